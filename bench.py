@@ -6,7 +6,12 @@ batch of 128 trajectories per GPU (BASELINE.json configs[1]; classifier-free-gui
 forwards per update), followed for N>1 by the single all-gather of the samples (configs[2], weak scaling:
 128 trajectories per GPU).  Prints ONE JSON line on rank 0.
 
-Extra objects on that line:
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).  --dump-outputs DIR
+also writes what the last timed step returned (samples.npy float32 [B*N,1,H,W], nfe.npy float64) for output-for-output
+comparison of two builds; the inputs (weights, labels, priors, Philox noise) are seeded, so the same arguments give the same
+inputs.  --full adds the measurements below, which take runs of their own after the timed region.
+
+Extra objects on the --full line:
   roofline     -- dominant kernel (the fp32-MFMA implicit-GEMM conv) algorithmic FLOP / its mean launch time,
                   measured with HIP events on the launch stream in an instrumented pass of the same workload
                   right after the timed region (per-launch events inside the timed region would perturb it);
@@ -14,6 +19,9 @@ Extra objects on that line:
                   compute-bound (48.6 FLOP/B layer-granular), so the HBM fraction is reported beside it.
   cpu_baseline -- oracle/rd_oracle_torch.py (a torch-CPU restatement pinned to the reference's fixtures; the
                   reference itself cannot travel to the GPU box) timed on this host's cores on a bounded sample.
+  variants     -- the other configurations (Langevin, [1,8,9], co-operative program off, large batches, CIFAR shape,
+                  training step), N=1 only.
+  ranks_seen / all_gather_us -- N>1: an all-reduce of ones over the group and the all-gather of the path timed alone.
 """
 import argparse
 import json
@@ -78,7 +86,12 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-variants', action='store_true', help='skip the Langevin / [1,8,9] / training-step variant measurements')
+    ap.add_argument('--full', action='store_true', help='after the headline, also measure roofline, variants, cpu_baseline '
+                    'and (N>1) ranks_seen / all_gather_us; the --no-* options above thin this set')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s samples and nfe to DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -160,9 +173,12 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
     assert x.shape[0] == B * world and bool(torch.isfinite(x).all()) and float(x.min()) >= 0 and float(x.max()) <= 1
-    # N > 1: how many ranks really took part (a sum of ones over the RCCL group) and what the one collective of the path costs alone
-    ranks_seen, gather_us = 1, None
-    if world > 1:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, nfe)
+    # N > 1 (--full): how many ranks really took part (a sum of ones over the RCCL group) and what the one collective of the path
+    # costs alone
+    ranks_seen, gather_us = (1 if world == 1 else None), None
+    if world > 1 and args.full:
         one = torch.ones(1, device=dev)
         dist.all_reduce(one)
         ranks_seen = int(one.item())
@@ -193,20 +209,33 @@ def main():
         'tflops_algorithmic': value * fwd_per_traj * GFLOP_PER_FORWARD / 1e3 / world,
         'plan': ctx0.path_info(), 'coop_fallback': coop_fallback, 'ranks_seen': ranks_seen, 'all_gather_us': gather_us,
     }
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         out['roofline'] = roofline(ge, model, cfg, sde, shape, labels, dev, args, value / world, fwd_per_traj)
-    if rank == 0 and world == 1 and not args.no_variants and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_variants and not args.no_roofline:
         try:
             out['variants'] = variants(ge, dev, args, labels)
         except Exception as e:                                   # noqa: BLE001  (the headline above is already measured)
             out['variants'] = {'error': f'{e.__class__.__name__}: {e}'[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(args, B)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, x, nfe, limit=64_000_000):
+    """What the last timed sampling call returned: samples.npy (float32 [B*N,1,H,W]; above `limit` bytes, the rows of a fixed
+    seeded sample, in order) and nfe.npy (float64 scalar)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    xs = x.float().cpu().numpy()
+    keep = limit // (xs[0].nbytes or 1)
+    if xs.shape[0] > keep:
+        xs = xs[np.sort(np.random.default_rng(0).choice(xs.shape[0], keep, replace=False))]
+    np.save(os.path.join(d, 'samples.npy'), xs)
+    np.save(os.path.join(d, 'nfe.npy'), np.array(nfe, dtype=np.float64))
 
 
 def profile_pass(model, cfg, shape, labels, dev, corrector):

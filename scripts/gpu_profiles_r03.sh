@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03; rm -rf $O; mkdir -p $O gpurun_out/prof gpurun_out/pmct
 export TMPDIR=/tmp
 set -x
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python3 bench.py --steps 1 --warmup 1 --num-scales 200 --no-cpu-baseline --no-variants > $O/bench_under_rocprof.json 2> $O/stderr_stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o stats -- python3 bench.py --steps 1 --warmup 1 --num-scales 200 --full --no-cpu-baseline --no-variants > $O/bench_under_rocprof.json 2> $O/stderr_stats.log
 echo step1 done
 BENCH40="python3 bench.py --steps 1 --warmup 0 --num-scales 40 --no-cpu-baseline --no-roofline --no-variants"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O -o sq1 -- $BENCH40 > /dev/null 2> $O/stderr_sq1.log && \

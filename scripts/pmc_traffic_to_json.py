@@ -1,4 +1,4 @@
-"""Turn the rocprofv3 --pmc passes of scripts/gpu_prof.sh (gpurun_out/prof/pmc_{fetch,write}_counter_collection.csv) into
+"""Turn the rocprofv3 --pmc passes of scripts/gpu_prof.sh ($O/pmc_{fetch,write}_counter_collection.csv, O=out/prof by default) into
 profiles/unet_traffic.json, the file bench.py's roofline.traffic is read from.  Records the kernel-source hash and commit the
 passes were taken on: bench.py emits traffic=null when the sources have changed since."""
 import csv, glob, json, os, subprocess, sys
@@ -8,7 +8,7 @@ from bench import csrc_sha16
 
 def mean_of(tag, kernel='unet_wg'):
     vals = []
-    for f in glob.glob(os.path.join(ROOT, 'gpurun_out', 'prof', f'pmc_{tag}_counter_collection.csv')):
+    for f in glob.glob(os.path.join(ROOT, os.environ.get('O', 'out/prof'), f'pmc_{tag}_counter_collection.csv')):
         for r in csv.DictReader(open(f)):
             if kernel in r.get('Kernel_Name', ''):
                 vals.append(float(r['Counter_Value']))
