@@ -2141,6 +2141,7 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
 #define RDMI_TCONV(NMT_, NCT_)                                                                                                        \
     do {                                                                                                                              \
         if (h) hipLaunchKernelGGL((tconv_kernel<NMT_, NCT_, true>), grid, dim3(RDMI_THREADS), lds, s, ca);                            \
+        else if (ca.drop_p > 0.f) hipLaunchKernelGGL((tconv_kernel<NMT_, NCT_, false, true>), grid, dim3(RDMI_THREADS), lds, s, ca);  \
         else hipLaunchKernelGGL((tconv_kernel<NMT_, NCT_, false>), grid, dim3(RDMI_THREADS), lds, s, ca);                             \
     } while (0)
             if (l.nmt == 4) { if (nct == 4) RDMI_TCONV(4, 4); else if (nct == 2) RDMI_TCONV(4, 2); else RDMI_TCONV(4, 1); }
@@ -2204,6 +2205,7 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
 }  // namespace
 
 #include "train_plan.h"
+#include "tiled_train.h"
 
 // ============================================================================================
 // C ABI
@@ -2314,6 +2316,10 @@ int rdmi_destroy(rdmi_ctx* c) {
         for (void* p : {(void*)T->x_in, (void*)T->out_buf, (void*)T->gout_buf, (void*)T->grads_int, (void*)T->d_seed}) if (p) (void)hipFree(p);
         for (void* p : {(void*)T->d_jobs, (void*)T->d_wb, (void*)T->d_int, (void*)T->gws, (void*)T->GA, (void*)T->GS, (void*)T->zero_bias, (void*)T->gdense, (void*)T->gta, (void*)T->gh1, (void*)T->four, (void*)T->sig_copy, (void*)T->lab_copy,
                         (void*)T->d_gemm_jobs, (void*)T->d_col_jobs}) if (p) (void)hipFree(p);
+        if (TiledTrain* tt = T->tiled) {
+            for (void* p : {(void*)tt->gws, (void*)tt->gfin, (void*)tt->act, (void*)tt->dact, (void*)tt->wslab, (void*)tt->cs, (void*)tt->gred, (void*)tt->gslab}) if (p) (void)hipFree(p);
+            delete tt;
+        }
         train_registry().erase(c);
         delete T;
     }

@@ -15,6 +15,7 @@
 //   softmax_rows_kernel, transpose_lc_kernel, nchw/nhwc copies: the rest of AttnBlockpp and the API boundary.
 #pragma once
 #include "common.h"
+#include "conv_kernel.h"     // dropout_scale
 
 struct TConvArgs {
     const float* srcA; const float* srcB;   // virtual input channels = concat(A [n][Ha*Wa][CA], B [n][Ha*Wa][CB]); B may be null
@@ -39,6 +40,8 @@ struct TConvArgs {
     const void* zeros;                      // 256 zero bytes (iconv_kernel: source of window pixels outside the image)
     int col_il;                             // bf16 packs: column interleave factor F of the weights (PackJob::col_il; 0 / 1: none)
     int out_bf16;                           // 1: `out` is a bf16 [n][Ho*Wo][Cout] tensor (the q | k | v projection feeding flash_attn_bf16_kernel, which rounds to bf16 anyway)
+    float drop_p; uint32_t op_id;           // training forward (fp32): Dropout_0 on the activated input (Conv_1 of a res block), Philox mask of element
+    const unsigned long long* seed_dev;     // (source pixel * Cin + channel) keyed by the step seed in device memory; the backward recomputes it.  p = 0: off
 };
 
 __host__ __device__ inline int tconv_trv(const TConvArgs& a) { return a.ntap == 1 ? a.TR : (a.TR - 1) * a.stride + 3; }
@@ -108,7 +111,7 @@ __device__ __forceinline__ void tconv_fetch(const TConvArgs& a, const TcGeom& g,
     }
 }
 
-template <bool BF16>
+template <bool BF16, bool DROP = false>
 __device__ __forceinline__ void tconv_commit(const TConvArgs& a, const TcGeom& g, int n, int c0, int npix, int tid, const f32x4 (&raw)[TC_MAXS]) {
     const int Cin = a.CA + a.CB;
     const int q = tid & 7, c = c0 + q * 4;
@@ -140,6 +143,11 @@ __device__ __forceinline__ void tconv_commit(const TConvArgs& a, const TcGeom& g
                 const float y = (v[j] - mean[j]) * (rstd[j] * gm[j]) + bt[j];
                 v[j] = a.act ? silu_f(y) : y;
             }
+        }
+        if (DROP && g.sp[k] >= 0 && c < Cin) {             // (a separate instantiation: the sampling kernels keep their registers)
+            const uint64_t sd = *a.seed_dev;
+            for (int j = 0; j < 4; ++j)
+                if (c + j < Cin) v[j] *= dropout_scale(sd, a.op_id, (uint64_t)g.sp[k] * Cin + c + j, a.drop_p);
         }
         if (BF16) {
             typedef unsigned int u32x2 __attribute__((vector_size(8)));
@@ -305,7 +313,7 @@ __device__ __forceinline__ void tconv_epilogue(const TConvArgs& a, f32x4 (&acc)[
     }
 }
 
-template <int NMT, int NCT, bool BF16>
+template <int NMT, int NCT, bool BF16, bool DROP = false>
 __global__ __launch_bounds__(RDMI_THREADS) void tconv_kernel(TConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lrow = lane & 15, kq = lane >> 4;
@@ -344,7 +352,7 @@ __global__ __launch_bounds__(RDMI_THREADS) void tconv_kernel(TConvArgs a) {
     f32x4 raw[TC_MAXS];
     tconv_fetch(a, geom, 0, tid, raw);
     for (int c0 = 0; c0 < a.Cv; c0 += 32) {
-        tconv_commit<BF16>(a, geom, n, c0, npix, tid, raw);
+        tconv_commit<BF16, DROP>(a, geom, n, c0, npix, tid, raw);
         __syncthreads();
         if (c0 + 32 < a.Cv) tconv_fetch(a, geom, c0 + 32, tid, raw);          // next slab's loads fly under this slab's MFMAs
         for (int t = 0; t < a.ntap; ++t) {

@@ -1,0 +1,270 @@
+// Training step on the TILED plan (fp32; shapes beyond one workgroup per sample, e.g. the CIFAR-shape model of BASELINE config #5).
+// Included by rdmi.hip after train_plan.h; rdmi_enable_training / rdmi_train_forward / rdmi_backward branch here on c->tiled.
+//
+// Forward: the ordinary tiled forward (run_tiled), with Dropout_0 applied in the GroupNorm+SiLU staging of every res block's Conv_1
+// (TConvArgs::drop_p: Philox mask of (step seed in device memory, launch index, source element)).  The tiled workspace is never
+// reused (TiledBuilder::talloc only grows), so every tensor the backward needs -- layer inputs, GroupNorm statistics, softmax
+// probabilities -- is still in place afterwards.
+// Backward: the launch list in reverse into a gradient twin of the workspace (same offsets), zeroed once per step: every
+// launch ADDS its input gradients into the twin, so a tensor read by several launches (skip tensors, the residual stream)
+// collects their sum; the gradient of a conv's output is complete when its producer is reached.  Kernels: tiled_bwd_kernels.h.
+#pragma once
+#include "tiled_bwd_kernels.h"
+
+namespace {
+
+struct TiledConvBwd {
+    int li = -1;                                       // launch index in c->tl
+    int pw[3] = {-1, -1, -1}, pb[3] = {-1, -1, -1};    // weight / bias parameters (q | k | v projection: three NIN matrices)
+    int co_blk = 0; long w_co = 0, w_ci = 0, w_t = 0;  // parameter layout: OIHW (3x3) or NIN [in][out]
+    int pg = -1, pbeta = -1;                           // GroupNorm gamma / beta
+    bool dropout = false;                              // Conv_1 of a res block: Dropout_0 on its activated input
+};
+
+struct TiledTrain {
+    std::map<int, TiledConvBwd> conv;                  // by launch index
+    float* gws = nullptr;                              // gradient twin of the tiled workspace (t_ws_per_sample * max_batch floats)
+    float* gfin = nullptr;                             // NHWC gradient of the network output
+    float *act = nullptr, *dact = nullptr, *wslab = nullptr, *cs = nullptr, *gred = nullptr, *gslab = nullptr;
+    static constexpr int MAX_SPLIT = 16;               // weight-gradient K splits (slab depth)
+    int last_B = 0; float drop_p = 0.f;
+};
+
+bool ends_with(const std::string& s, const char* t) { const size_t n = std::strlen(t); return s.size() >= n && s.compare(s.size() - n, n, t) == 0; }
+
+inline float* tl_gptr(rdmi_ctx* c, const TiledTrain& tt, size_t off) {
+    if (off == rdmi_ctx::TLaunch::NONE || off == rdmi_ctx::TLaunch::XIN) return nullptr;
+    return tt.gws + off * (size_t)c->max_batch;
+}
+
+int tiled_enable_training(rdmi_ctx* c, TrainPlan& T) {
+    if (c->arch.compute_dtype != 0) return fail("training on the tiled plan is built for fp32 only (train_dtype='bf16' on this shape is not built)");
+    TiledTrain* tt = new TiledTrain();
+    T.tiled = tt;
+    const size_t NBmax = (size_t)c->max_batch;
+    T.poff.resize(c->params.size());
+    T.ptotal = 0;
+    for (size_t i = 0; i < c->params.size(); ++i) { T.poff[i] = T.ptotal; T.ptotal += c->params[i].numel; }
+    size_t act_f = 1, dact_f = 1, slab_f = 1; int cmax = 64;
+    for (size_t li = 0; li < c->tl.size(); ++li) {
+        const rdmi_ctx::TLaunch& l = c->tl[li];
+        if (l.kind == 6 || l.kind == 7 || l.pre) return fail("tiled training: launch %s is a bf16-plan launch", l.name.c_str());
+        if (l.kind != 0) continue;
+        const TConvArgs& a = l.conv;
+        const int Cin = a.CA + a.CB;
+        TiledConvBwd b; b.li = (int)li;
+        if (ends_with(l.name, ".qkv")) {
+            const std::string pre = l.name.substr(0, l.name.size() - 4);
+            b.co_blk = a.Cout / 3; b.w_co = 1; b.w_ci = b.co_blk; b.w_t = 0;
+            for (int i = 0; i < 3; ++i) {
+                b.pw[i] = c->pindex.at(pre + ".NIN_" + std::to_string(i) + ".W");
+                b.pb[i] = c->pindex.at(pre + ".NIN_" + std::to_string(i) + ".b");
+            }
+        } else if (a.ntap == 1) {
+            b.pw[0] = c->pindex.at(l.name + ".W"); b.pb[0] = c->pindex.at(l.p_bias);
+            b.co_blk = a.Cout; b.w_co = 1; b.w_ci = a.Cout; b.w_t = 0;
+        } else {
+            b.pw[0] = c->pindex.at(l.name + ".weight"); b.pb[0] = c->pindex.at(l.p_bias);
+            b.co_blk = a.Cout; b.w_co = (long)Cin * 9; b.w_ci = 9; b.w_t = 1;
+        }
+        if (!l.p_gamma.empty()) {
+            if (a.up || a.stride != 1) return fail("tiled training: GroupNorm ahead of a resampling conv (%s)", l.name.c_str());
+            b.pg = c->pindex.at(l.p_gamma); b.pbeta = c->pindex.at(l.p_beta);
+            act_f = std::max(act_f, (size_t)a.Hv * a.Wv * Cin);
+        }
+        b.dropout = ends_with(l.name, ".Conv_1");
+        if (!l.in_is_x) dact_f = std::max(dact_f, (size_t)a.Hv * a.Wv * Cin);
+        slab_f = std::max(slab_f, (size_t)a.ntap * a.Cout * Cin * TiledTrain::MAX_SPLIT);
+        cmax = std::max(cmax, std::max(a.Cout, Cin));
+        tt->conv[(int)li] = b;
+    }
+    const size_t E = (size_t)c->H * c->W * c->arch.channels, Mp = (size_t)pad16(c->max_batch);
+    HIP_OK(hipMalloc((void**)&tt->gws, c->t_ws_per_sample * NBmax * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->gfin, E * NBmax * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->act, act_f * NBmax * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->dact, dact_f * NBmax * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->wslab, slab_f * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->cs, (size_t)cmax * NBmax * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->gslab, (size_t)cmax * 2 * NBmax * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&tt->gred, (size_t)32 * 2 * NBmax * sizeof(float)));
+    // embedding backward (embed_backward) and step inputs
+    HIP_OK(hipMalloc((void**)&T.gdense, Mp * c->dense_total * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&T.gta, Mp * c->temb * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&T.gh1, Mp * c->temb * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&T.four, Mp * 2 * c->arch.nf * sizeof(float)));
+    T.emb_jobs = std::max(64, 2 * (c->dense_total / 32 + 1) + 8);   // two jobs per res block (>= 32 channels each) + the time / label stages
+    HIP_OK(hipMalloc((void**)&T.d_gemm_jobs, (size_t)T.emb_jobs * sizeof(SgemmArgs)));
+    HIP_OK(hipMalloc((void**)&T.d_col_jobs, (size_t)T.emb_jobs * sizeof(ColsumJob)));
+    T.h_gemm_jobs.reserve((size_t)T.emb_jobs); T.h_col_jobs.reserve((size_t)T.emb_jobs);
+    HIP_OK(hipMalloc((void**)&T.sig_copy, Mp * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&T.lab_copy, Mp * std::max(1, c->arch.num_classes) * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&T.d_seed, 64));
+    HIP_OK(hipMemset(T.d_seed, 0, 64));
+    HIP_OK(hipHostMalloc((void**)&T.h_seed, 64 * sizeof(unsigned long long), 0));
+    T.use_graph = false;                               // plain launches on the caller's stream
+    T.ready = true;
+    return 0;
+}
+
+int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* sigma, const float* labels, float* out, int B, float dropout_p,
+                        uint64_t seed, hipStream_t s) {
+    TiledTrain& tt = *T.tiled;
+    if (int e = do_repack(c, s)) return e;
+    HIP_OK(hipMemcpyAsync(T.sig_copy, sigma, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (labels) HIP_OK(hipMemcpyAsync(T.lab_copy, labels, (size_t)B * c->arch.num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
+    T.seed_slot = (T.seed_slot + 1) & 63;
+    T.h_seed[T.seed_slot] = seed;
+    HIP_OK(hipMemcpyAsync(T.d_seed, T.h_seed + T.seed_slot, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    for (auto& kv : tt.conv)
+        if (kv.second.dropout) {
+            TConvArgs& a = c->tl[(size_t)kv.first].conv;
+            a.drop_p = dropout_p; a.op_id = (uint32_t)kv.first; a.seed_dev = T.d_seed;
+        }
+    FwdIn f{x, 0, T.sig_copy, 0, 0.f, 0, 0.f, 0.f, labels ? T.lab_copy : nullptr, B, out, B};
+    const int e = run_forward(c, f, s);
+    for (auto& kv : tt.conv) { TConvArgs& a = c->tl[(size_t)kv.first].conv; a.drop_p = 0.f; a.seed_dev = nullptr; }   // sampling stays p = 0
+    if (c->profiling) prof_collect(c);
+    tt.last_B = B; tt.drop_p = dropout_p; T.last_B = B;
+    return e;
+}
+
+inline unsigned tb_blocks(long n) { return (unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS); }
+
+// backward of one conv launch: G (in place) -> bias / Dense_0 -> weight gradient -> data gradient -> GroupNorm / resampling adjoint
+int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ctx::TLaunch& l, const TiledConvBwd& b, float* grads_flat, int NB, hipStream_t s) {
+    const TConvArgs& a = l.conv;
+    const int Cin = a.CA + a.CB, HWo = a.Ho * a.Wo, HWv = a.Hv * a.Wv;
+    auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
+    float* G = l.out_is_final ? tt.gfin : tl_gptr(c, tt, l.oOut);
+    {   // G = out_scale / sigma_n * dY (in place); residual gradient; column sums
+        const float* sig = (l.out_is_final && c->arch.scale_by_sigma) ? T.sig_copy : nullptr;
+        ProfScope ps(c, s, "tb_outgrad_kernel", 0);
+        hipLaunchKernelGGL(tb_outgrad_kernel, dim3((unsigned)ceil_div(a.Cout, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, (const float*)G, G,
+                           tl_gptr(c, tt, l.oResid), tt.cs, HWo, a.Cout, a.out_scale, sig);
+    }
+    {
+        ProfScope ps(c, s, "tb_bias_kernel", 0);
+        hipLaunchKernelGGL(tb_bias_kernel, dim3((unsigned)ceil_div(a.Cout, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.cs, NB, a.Cout,
+                           pgrad(b.pb[0]), pgrad(b.pb[1]), pgrad(b.pb[2]), b.co_blk, l.use_dense ? T.gdense : (float*)nullptr, c->dense_total, a.dense_off);
+    }
+    const bool gn = b.pg >= 0;
+    TbGnArgs g{};
+    g.A = a.srcA; g.B = a.srcB; g.CA = a.CA; g.CB = a.CB; g.HW = a.Ha * a.Wa; g.NB = NB;
+    g.stats = a.stats; g.G = a.G; g.Cg = a.Cg; g.act = a.act; g.gamma = a.gamma; g.beta = a.beta;
+    g.drop_p = b.dropout ? tt.drop_p : 0.f; g.op_id = (uint32_t)b.li; g.seed_dev = T.d_seed;
+    g.ACT = tt.act; g.dACT = tt.dact; g.red = tt.gred; g.gslab = tt.gslab;
+    g.gA = tl_gptr(c, tt, l.oA); g.gB = tl_gptr(c, tt, l.oB);
+    g.up = a.up; g.Hv = a.Hv; g.Wv = a.Wv; g.has_gn = gn ? 1 : 0;
+    if (gn) {   // the activated input, recomputed (GroupNorm + SiLU + the step's dropout mask)
+        ProfScope ps(c, s, "tb_act_kernel", 0);
+        hipLaunchKernelGGL(tb_act_kernel, dim3(tb_blocks((long)NB * HWv * Cin)), dim3(RDMI_THREADS), 0, s, g);
+    }
+    {   // weight gradient: K = samples x output pixels split into <= MAX_SPLIT chunks, slab summed in a fixed order
+        TbGemmArgs w{};
+        w.M = a.Cout; w.N = Cin; w.K = NB * HWo;
+        w.Hv = a.Hv; w.Wv = a.Wv; w.Ho = a.Ho; w.Wo = a.Wo; w.stride = a.stride; w.pad = a.pad_lo; w.ntap = a.ntap; w.Cin = Cin; w.Cout = a.Cout;
+        w.G = G;
+        if (gn) { w.X = tt.act; w.X2 = nullptr; w.CA = Cin; w.CB = 0; w.Ha = a.Hv; w.Wa = a.Wv; w.up = 0; }
+        else { w.X = a.srcA; w.X2 = a.srcB; w.CA = a.CA; w.CB = a.CB; w.Ha = a.Ha; w.Wa = a.Wa; w.up = a.up; }
+        const long tiles = (long)ceil_div(a.Cout, 64) * ceil_div(Cin, 64) * a.ntap;
+        int ns = (int)std::max(1L, std::min((long)TiledTrain::MAX_SPLIT, 1024 / tiles));
+        ns = std::max(1, std::min(ns, ceil_div(w.K, 256)));
+        w.kchunk = ceil_div(ceil_div(w.K, ns), 16) * 16; ns = ceil_div(w.K, w.kchunk); w.nsplit = ns;
+        w.out = tt.wslab;
+        {
+            ProfScope ps(c, s, "tb_gemm_kernel<wgrad>", 2.0 * NB * HWo * a.ntap * (double)a.Cout * Cin);
+            hipLaunchKernelGGL(tb_gemm_kernel<2>, dim3((unsigned)ceil_div(a.Cout, 64), (unsigned)ceil_div(Cin, 64), (unsigned)(a.ntap * ns)), dim3(RDMI_THREADS), 0, s, w);
+        }
+        ProfScope ps(c, s, "tb_wgrad_reduce_kernel", 0);
+        hipLaunchKernelGGL(tb_wgrad_reduce_kernel, dim3(tb_blocks((long)a.ntap * a.Cout * Cin)), dim3(RDMI_THREADS), 0, s, (const float*)tt.wslab, ns, a.ntap,
+                           a.Cout, Cin, pgrad(b.pw[0]), pgrad(b.pw[1]), pgrad(b.pw[2]), b.co_blk, b.w_co, b.w_ci, b.w_t);
+    }
+    if (l.in_is_x) return 0;                           // no gradient w.r.t. the network input
+    {   // data gradient over the virtual input grid
+        TbGemmArgs d{};
+        d.M = NB * HWv; d.N = Cin; d.K = a.ntap * a.Cout;
+        d.Hv = a.Hv; d.Wv = a.Wv; d.Ho = a.Ho; d.Wo = a.Wo; d.stride = a.stride; d.pad = a.pad_lo; d.ntap = a.ntap; d.Cin = Cin; d.Cout = a.Cout;
+        d.G = G;
+        for (int i = 0; i < 3; ++i) d.W[i] = b.pw[i] >= 0 ? c->params[(size_t)b.pw[i]].ptr : nullptr;
+        d.co_blk = b.co_blk; d.w_co = b.w_co; d.w_ci = b.w_ci; d.w_t = b.w_t;
+        d.out = tt.dact;
+        ProfScope ps(c, s, "tb_gemm_kernel<dgrad>", 2.0 * NB * HWo * a.ntap * (double)a.Cout * Cin);
+        hipLaunchKernelGGL(tb_gemm_kernel<1>, dim3((unsigned)ceil_div(d.M, 64), (unsigned)ceil_div(Cin, 64), 1), dim3(RDMI_THREADS), 0, s, d);
+    }
+    if (gn) {
+        {
+            ProfScope ps(c, s, "tb_gn_red_kernel", 0);
+            hipLaunchKernelGGL(tb_gn_red_kernel, dim3((unsigned)a.G, (unsigned)NB), dim3(RDMI_THREADS), 0, s, g);
+        }
+        ProfScope ps(c, s, "tb_rowsum_kernel", 0);
+        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab, NB, Cin, 2, 0, pgrad(b.pg));
+        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab, NB, Cin, 2, 1, pgrad(b.pbeta));
+    }
+    ProfScope ps(c, s, "tb_src_grad_kernel", 0);
+    hipLaunchKernelGGL(tb_src_grad_kernel, dim3(tb_blocks((long)NB * a.Ha * a.Wa * Cin)), dim3(RDMI_THREADS), 0, s, g);
+    return 0;
+}
+
+// AttnBlockpp core backward on the stored probabilities P (launch `pv`; q | k | v from launch `qk`):
+//   dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dP o P)), dQ = alpha dS K, dK = alpha dS^T Q   (dP / dS live in the twin of S)
+int tiled_attn_backward(rdmi_ctx* c, TiledTrain& tt, const rdmi_ctx::TLaunch& qk, const rdmi_ctx::TLaunch& pv, int NB, hipStream_t s) {
+    const int L = pv.gemm.M, C = pv.gemm.N;
+    const long C3 = 3L * C, LL = (long)L * L, LC3 = L * C3, LC = (long)L * C;
+    const float* P = tl_ptr(c, pv.oA);
+    const float* qkv = tl_ptr(c, qk.oA);
+    float* dS = tl_gptr(c, tt, pv.oA);
+    const float* dO = tl_gptr(c, tt, pv.oC);
+    float* dqkv = tl_gptr(c, tt, qk.oA);
+    const float alpha = qk.gemm.alpha;
+    auto gemm = [&](int M, int N, int K, const float* A, long ab, long am, long ak, const float* B, long bb, long bk, long bn, float* Cp, long cb, long cm, long cn,
+                    float al) {
+        TbGemmArgs g{};
+        g.M = M; g.N = N; g.K = K; g.A = A; g.a_b = ab; g.a_m = am; g.a_k = ak; g.B = B; g.b_b = bb; g.b_k = bk; g.b_n = bn;
+        g.C = Cp; g.c_b = cb; g.c_m = cm; g.c_n = cn; g.alpha = al;
+        ProfScope ps(c, s, "tb_gemm_kernel<attn>", 2.0 * M * N * K * NB);
+        hipLaunchKernelGGL(tb_gemm_kernel<0>, dim3((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, g);
+    };
+    gemm(L, C, L, P, LL, 1, L, dO, LC, C, 1, dqkv + 2 * C, LC3, C3, 1, 1.f);                 // dV[j][c] = sum_i P[i][j] dO[i][c]
+    gemm(L, L, C, dO, LC, C, 1, qkv + 2 * C, LC3, 1, C3, dS, LL, L, 1, 1.f);                 // dP[i][j] = sum_c dO[i][c] V[j][c]
+    {
+        ProfScope ps(c, s, "tb_softmax_bwd_kernel", 0);
+        hipLaunchKernelGGL(tb_softmax_bwd_kernel, dim3((unsigned)ceil_div(NB * L, 4)), dim3(RDMI_THREADS), 0, s, P, dS, (long)NB * L, L);
+    }
+    gemm(L, C, L, dS, LL, L, 1, qkv + C, LC3, C3, 1, dqkv, LC3, C3, 1, alpha);              // dQ[i][c] = alpha sum_j dS[i][j] K[j][c]
+    gemm(L, C, L, dS, LL, 1, L, qkv, LC3, C3, 1, dqkv + C, LC3, C3, 1, alpha);              // dK[j][c] = alpha sum_i dS[i][j] Q[i][c]
+    return 0;
+}
+
+int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grads_flat, size_t grads_numel, hipStream_t s) {
+    TiledTrain& tt = *T.tiled;
+    if (grads_numel != T.ptotal) return fail("grads buffer holds %zu floats, the model has %zu parameters", grads_numel, T.ptotal);
+    const int NB = tt.last_B;
+    if (NB < 1) return fail("rdmi_backward before rdmi_train_forward");
+    const size_t NBmax = (size_t)c->max_batch;
+    const int HW = c->H * c->W, Cc = c->arch.channels;
+    // every parameter gradient below is a store; time_embed.W (not trained) stays zero.  The twin takes sums: zeroed (all of it,
+    // t_ws_per_sample * max_batch floats -- the tensors are [tensor][sample] blocks, so the first NB samples are not one range)
+    HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
+    HIP_OK(hipMemsetAsync(tt.gws, 0, c->t_ws_per_sample * NBmax * sizeof(float), s));
+    HIP_OK(hipMemsetAsync(T.gdense, 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(tb_blocks((long)NB * HW * Cc)), dim3(RDMI_THREADS), 0, s, grad_out, tt.gfin, NB, HW, Cc, 0);
+    for (int li = (int)c->tl.size() - 1; li >= 0; --li) {
+        const rdmi_ctx::TLaunch& l = c->tl[(size_t)li];
+        if (l.kind == 0) {
+            if (int e = tiled_conv_backward(c, T, tt, l, tt.conv.at(li), grads_flat, NB, s)) return e;
+        } else if (l.kind == 2 && ends_with(l.name, ".pv")) {
+            const std::string qk_name = l.name.substr(0, l.name.size() - 3) + ".qk";
+            int qi = li - 1;
+            while (qi >= 0 && c->tl[(size_t)qi].name != qk_name) --qi;
+            if (qi < 0) return fail("tiled training: no launch %s", qk_name.c_str());
+            if (int e = tiled_attn_backward(c, tt, c->tl[(size_t)qi], l, NB, s)) return e;
+        }
+        // kinds 1 / 5 (GroupNorm statistics): their gradient is part of the GroupNorm backward; 3 / 4 and `qk`: inside the attention backward
+        HIP_OK(hipGetLastError());
+    }
+    if (int e = embed_backward(c, T, grads_flat, NB, s)) return e;
+    if (c->profiling) prof_collect(c);
+    return 0;
+}
+
+}  // namespace

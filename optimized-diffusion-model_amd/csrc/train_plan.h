@@ -16,8 +16,11 @@ struct BwdConv {
     int p_w = -1, p_b = -1, p_gamma = -1, p_beta = -1, p_wsc = -1, p_bsc = -1;   // parameter indices (flat-grad slices)
 };
 
+struct TiledTrain;                       // training on the tiled plan (csrc/tiled_train.h)
+
 struct TrainPlan {
     bool ready = false;
+    TiledTrain* tiled = nullptr;         // non-null: the context runs the tiled plan, and the members below serve its embedding backward
     std::vector<BwdConv> convs;          // one per forward conv op (same order as c->ops; attention ops are looked up separately)
     std::vector<PackJob> jobs; std::vector<int> job_param;
     PackJob* d_jobs = nullptr;
@@ -39,7 +42,8 @@ struct TrainPlan {
     std::vector<size_t> poff;            // flat-gradient offset of every parameter
     size_t ptotal = 0;
     float drop_p = 0.f; uint64_t seed = 0; int last_B = 0; int label_rows = 0;
-    SgemmArgs* d_gemm_jobs = nullptr; ColsumJob* d_col_jobs = nullptr;   // job tables of the embedding backward (64 entries each)
+    SgemmArgs* d_gemm_jobs = nullptr; ColsumJob* d_col_jobs = nullptr;   // job tables of the embedding backward (emb_jobs entries each)
+    int emb_jobs = 64;                   // (the tiled plan's CIFAR shape has 35 res blocks: two Dense_0 jobs each)
     std::vector<SgemmArgs> h_gemm_jobs; std::vector<ColsumJob> h_col_jobs;
     std::vector<SgemmArgs> m_gemm_jobs; std::vector<ColsumJob> m_col_jobs;   // host mirror of what the device tables hold (uploads only on change)
     // ---- launch graphs (RDMI_TRAIN_GRAPH=0: plain launches).  The ~100 launches of the train-mode forward and the ~250 of the backward
@@ -74,6 +78,11 @@ struct rdmi_train { TrainPlan t; };
 namespace {
 
 std::map<rdmi_ctx*, TrainPlan*>& train_registry() { static std::map<rdmi_ctx*, TrainPlan*> r; return r; }
+
+int tiled_enable_training(rdmi_ctx* c, TrainPlan& T);
+int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* sigma, const float* labels, float* out, int B, float dropout_p,
+                        uint64_t seed, hipStream_t s);
+int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grads_flat, size_t grads_numel, hipStream_t s);
 
 // split the batch so that ~1000 workgroups exist whatever the layer's channel counts
 int launch_wgrad(WgradArgs w, hipStream_t s) {
@@ -367,9 +376,10 @@ int rdmi_enable_training(rdmi_ctx* c) {
     if (get_train(c)) return 0;
     TrainPlan* T = new TrainPlan();
     int e = 0;
-    try { e = build_train_plan(c, *T); } catch (const std::exception& ex) { e = fail("training plan: %s", ex.what()); }
+    try { e = c->tiled ? tiled_enable_training(c, *T) : build_train_plan(c, *T); } catch (const std::exception& ex) { e = fail("training plan: %s", ex.what()); }
     if (e) { delete T; return e; }
     train_registry()[c] = T;
+    if (c->tiled) return 0;
     // The training forward as ONE workgroup-resident launch (the S = 1 fused program + a stash of every layer output + Dropout_0
     // in the GroupNorm_1 epilogues) instead of ~100 layer-plan launches.  RDMI_TRAIN_FUSED=0, or a shape the planner cannot fit,
     // keeps the layer plan's forward.
@@ -471,6 +481,113 @@ int run_recorded(TrainPlan& T, hipGraphExec_t& exec, std::vector<unsigned long l
     return 0;
 }
 
+// ---- embedding backward: Dense_0 (x17) -> SiLU -> [label_emb, time_mlp.2] -> SiLU -> time_mlp.0, from T.gdense (the per-sample
+//      Dense_0 column gradients) and the forward's d_temb / d_h1.  Shared by the layer plan and the tiled plan (csrc/tiled_train.h).
+int embed_backward(rdmi_ctx* c, TrainPlan& T, float* grads_flat, int NB, hipStream_t s) {
+    auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
+    // Independent GEMMs and bias column sums of one stage go out as one job-table launch each (tables staged in T.h_*: they live until the next call).
+    const int Tm = c->temb, DT = c->dense_total, nf = c->arch.nf;
+    {
+        auto& GJ = T.h_gemm_jobs; auto& CJ = T.h_col_jobs;
+        GJ.clear(); CJ.clear();
+        size_t g_used = 0, c_used = 0;                         // entries of the device tables already consumed by earlier launches
+        T.m_gemm_jobs.resize((size_t)T.emb_jobs); T.m_col_jobs.resize((size_t)T.emb_jobs);
+        auto flush_gemm = [&]() -> int {
+            const size_t nj = GJ.size() - g_used;
+            if (!nj) return 0;
+            if (GJ.size() > (size_t)T.emb_jobs) return fail("embedding backward: %zu GEMM jobs", GJ.size());
+            int mm = 0, mn = 0, mk = 0;
+            for (size_t i = g_used; i < GJ.size(); ++i) { mm = std::max(mm, GJ[i].M); mn = std::max(mn, GJ[i].N); if (!GJ[i].no_split) mk = std::max(mk, GJ[i].K); }
+            const int ks = std::max(1, std::min(ceil_div(std::max(mk, 1), 64), 16));
+            if (std::memcmp(T.m_gemm_jobs.data() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs)) != 0) {   // same buffers as last step: already resident
+                std::memcpy(T.m_gemm_jobs.data() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs));
+                HIP_OK(hipMemcpyAsync(T.d_gemm_jobs + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs), hipMemcpyHostToDevice, s));
+            }
+            hipLaunchKernelGGL(small_gemm_jobs_kernel, dim3((unsigned)ceil_div(mm, 64), (unsigned)ceil_div(mn, 64), (unsigned)(nj * ks)), dim3(RDMI_THREADS), 0, s,
+                               (const SgemmArgs*)(T.d_gemm_jobs + g_used), ks);
+            g_used = GJ.size();
+            return 0;
+        };
+        auto flush_col = [&](int M, int ldx) -> int {
+            const size_t nj = CJ.size() - c_used;
+            if (!nj) return 0;
+            if (CJ.size() > (size_t)T.emb_jobs) return fail("embedding backward: %zu column-sum jobs", CJ.size());
+            int mc = 0;
+            for (size_t i = c_used; i < CJ.size(); ++i) mc = std::max(mc, CJ[i].C);
+            if (std::memcmp(T.m_col_jobs.data() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob)) != 0) {
+                std::memcpy(T.m_col_jobs.data() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob));
+                HIP_OK(hipMemcpyAsync(T.d_col_jobs + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob), hipMemcpyHostToDevice, s));
+            }
+            hipLaunchKernelGGL(colsum_jobs_kernel, dim3((unsigned)ceil_div(mc, 64), (unsigned)std::max(1, std::min(64, M / 64)), (unsigned)nj), dim3(RDMI_THREADS), 0, s,
+                               (const ColsumJob*)(T.d_col_jobs + c_used), M, ldx);
+            c_used = CJ.size();
+            return 0;
+        };
+        Layout L = build_layout(c);
+        std::vector<std::pair<std::string, int>> blocks;
+        for (auto& d : L.down) blocks.push_back({d.name, d.cout});
+        blocks.push_back({"mid_block1", L.mid_ch}); blocks.push_back({"mid_block2", L.mid_ch});
+        for (auto& u : L.up) blocks.push_back({u.name, u.cout});
+        HIP_OK(hipMemsetAsync(T.gta, 0, (size_t)pad16(c->max_batch) * Tm * sizeof(float), s));
+        int off = 0;
+        for (auto& bl : blocks) {
+            const int pw = c->pindex.at(bl.first + ".Dense_0.weight"), pb = c->pindex.at(bl.first + ".Dense_0.bias");
+            SgemmArgs g{};   // dWd[co][k] = sum_n gdense[n][off+co] * silu(temb[n][k])
+            g.A = T.gdense + off; g.a_m = 1; g.a_k = DT; g.a_act = 0;
+            g.B = c->d_temb; g.b_k = Tm; g.b_n = 1; g.b_act = 1;
+            g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1; g.accumulate = 0; g.M = bl.second; g.N = Tm; g.K = NB;
+            GJ.push_back(g);
+            CJ.push_back(ColsumJob{T.gdense + off, pgrad(pb), bl.second, 0});
+            SgemmArgs h{};   // gta[n][k] += sum_co gdense[n][off+co] * Wd[co][k]   (gta zeroed above; the 17 blocks add with atomics)
+            h.A = T.gdense + off; h.a_m = DT; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1;
+            h.C = T.gta; h.c_m = Tm; h.c_n = 1; h.accumulate = 1; h.M = NB; h.N = Tm; h.K = bl.second; h.no_split = 1;
+            GJ.push_back(h);
+            off += bl.second;
+        }
+        if (int e = flush_gemm()) return e;
+        if (int e = flush_col(NB, DT)) return e;
+        hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gta, (const float*)c->d_temb, (long)NB * Tm);
+        // gta is now g(temb)
+        if (c->arch.conditional) {
+            const int pw = c->pindex.at("label_emb.weight"), pb = c->pindex.at("label_emb.bias"), nc = c->arch.num_classes;
+            SgemmArgs g{};   // dWl[k][cl] = sum_n gtemb[n][k] * labels[n][cl]
+            g.A = T.gta; g.a_m = 1; g.a_k = Tm; g.B = T.lab_copy; g.b_k = nc; g.b_n = 1; g.C = pgrad(pw); g.c_m = nc; g.c_n = 1;
+            g.M = Tm; g.N = nc; g.K = NB;
+            GJ.push_back(g);
+            CJ.push_back(ColsumJob{T.gta, pgrad(pb), Tm, 0});
+        }
+        {
+            const int pw = c->pindex.at("time_mlp.2.weight"), pb = c->pindex.at("time_mlp.2.bias");
+            SgemmArgs g{};   // dW2[k][j] = sum_n gtemb[n][k] * silu(h1[n][j])
+            g.A = T.gta; g.a_m = 1; g.a_k = Tm; g.B = c->d_h1; g.b_k = Tm; g.b_n = 1; g.b_act = 1; g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1;
+            g.M = Tm; g.N = Tm; g.K = NB;
+            GJ.push_back(g);
+            CJ.push_back(ColsumJob{T.gta, pgrad(pb), Tm, 0});
+            SgemmArgs h{};   // gh1[n][j] = sum_k gtemb[n][k] * W2[k][j]
+            h.A = T.gta; h.a_m = Tm; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1; h.C = T.gh1; h.c_m = Tm; h.c_n = 1;
+            h.M = NB; h.N = Tm; h.K = Tm; h.no_split = 1;
+            GJ.push_back(h);
+            if (int e = flush_gemm()) return e;
+            if (int e = flush_col(NB, Tm)) return e;
+            hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gh1, (const float*)c->d_h1, (long)NB * Tm);
+        }
+        {
+            const int pw = c->pindex.at("time_mlp.0.weight"), pb = c->pindex.at("time_mlp.0.bias");
+            hipLaunchKernelGGL(fourier_kernel, dim3((unsigned)ceil_div(NB * 2 * nf, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)T.sig_copy,
+                               c->params[(size_t)c->pindex.at("time_embed.W")].ptr, T.four, NB, nf);
+            SgemmArgs g{};   // dW0[j][f] = sum_n gh1[n][j] * four[n][f]
+            g.A = T.gh1; g.a_m = 1; g.a_k = Tm; g.B = T.four; g.b_k = 2 * nf; g.b_n = 1; g.C = pgrad(pw); g.c_m = 2 * nf; g.c_n = 1;
+            g.M = Tm; g.N = 2 * nf; g.K = NB;
+            GJ.push_back(g);
+            CJ.push_back(ColsumJob{T.gh1, pgrad(pb), Tm, 0});
+            if (int e = flush_gemm()) return e;
+            if (int e = flush_col(NB, Tm)) return e;
+        }
+        HIP_OK(hipGetLastError());
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -483,6 +600,7 @@ int rdmi_train_forward(rdmi_ctx* c, const float* x, const float* sigma, const fl
     if (!T) return fail("call rdmi_enable_training first");
     if (B < 1 || B > c->max_batch) return fail("batch %d outside [1, %d]", B, c->max_batch);
     hipStream_t s = (hipStream_t)stream;
+    if (c->tiled) return tiled_train_forward(c, *T, x, sigma, labels, out, B, dropout_p, seed, s);
     if (int e = train_refresh_params(c, *T, s)) return e;
     T->drop_p = dropout_p; T->seed = seed; T->last_B = B;
     // inputs -> fixed addresses; the seed -> the device word the kernels read
@@ -525,6 +643,7 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
     TrainPlan* Tp = get_train(c);
     if (!Tp) return fail("call rdmi_enable_training first");
     TrainPlan& T = *Tp;
+    if (c->tiled) return tiled_backward(c, T, grad_out, grads_flat, grads_numel, (hipStream_t)stream);
     if (grads_numel != T.ptotal) return fail("grads buffer holds %zu floats, the model has %zu parameters", grads_numel, T.ptotal);
     hipStream_t s0 = (hipStream_t)stream;
     const int NB = T.last_B;
@@ -682,107 +801,7 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
     }
     if (int e = flush_wgrads(((nconv - 1) % (2 * grp)) / grp)) return e;
 
-    // ---- embedding backward: Dense_0 (x17) -> SiLU -> [label_emb, time_mlp.2] -> SiLU -> time_mlp.0.  Independent GEMMs and
-    //      bias column sums of one stage go out as one job-table launch each (tables staged in T.h_*: they live until the next call).
-    const int Tm = c->temb, DT = c->dense_total, nf = c->arch.nf;
-    {
-        auto& GJ = T.h_gemm_jobs; auto& CJ = T.h_col_jobs;
-        GJ.clear(); CJ.clear();
-        size_t g_used = 0, c_used = 0;                         // entries of the device tables already consumed by earlier launches
-        T.m_gemm_jobs.resize(64); T.m_col_jobs.resize(64);
-        auto flush_gemm = [&]() -> int {
-            const size_t nj = GJ.size() - g_used;
-            if (!nj) return 0;
-            if (GJ.size() > 64) return fail("embedding backward: %zu GEMM jobs", GJ.size());
-            int mm = 0, mn = 0, mk = 0;
-            for (size_t i = g_used; i < GJ.size(); ++i) { mm = std::max(mm, GJ[i].M); mn = std::max(mn, GJ[i].N); if (!GJ[i].no_split) mk = std::max(mk, GJ[i].K); }
-            const int ks = std::max(1, std::min(ceil_div(std::max(mk, 1), 64), 16));
-            if (std::memcmp(T.m_gemm_jobs.data() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs)) != 0) {   // same buffers as last step: already resident
-                std::memcpy(T.m_gemm_jobs.data() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs));
-                HIP_OK(hipMemcpyAsync(T.d_gemm_jobs + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs), hipMemcpyHostToDevice, s));
-            }
-            hipLaunchKernelGGL(small_gemm_jobs_kernel, dim3((unsigned)ceil_div(mm, 64), (unsigned)ceil_div(mn, 64), (unsigned)(nj * ks)), dim3(RDMI_THREADS), 0, s,
-                               (const SgemmArgs*)(T.d_gemm_jobs + g_used), ks);
-            g_used = GJ.size();
-            return 0;
-        };
-        auto flush_col = [&](int M, int ldx) -> int {
-            const size_t nj = CJ.size() - c_used;
-            if (!nj) return 0;
-            if (CJ.size() > 64) return fail("embedding backward: %zu column-sum jobs", CJ.size());
-            int mc = 0;
-            for (size_t i = c_used; i < CJ.size(); ++i) mc = std::max(mc, CJ[i].C);
-            if (std::memcmp(T.m_col_jobs.data() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob)) != 0) {
-                std::memcpy(T.m_col_jobs.data() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob));
-                HIP_OK(hipMemcpyAsync(T.d_col_jobs + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob), hipMemcpyHostToDevice, s));
-            }
-            hipLaunchKernelGGL(colsum_jobs_kernel, dim3((unsigned)ceil_div(mc, 64), (unsigned)std::max(1, std::min(64, M / 64)), (unsigned)nj), dim3(RDMI_THREADS), 0, s,
-                               (const ColsumJob*)(T.d_col_jobs + c_used), M, ldx);
-            c_used = CJ.size();
-            return 0;
-        };
-        Layout L = build_layout(c);
-        std::vector<std::pair<std::string, int>> blocks;
-        for (auto& d : L.down) blocks.push_back({d.name, d.cout});
-        blocks.push_back({"mid_block1", L.mid_ch}); blocks.push_back({"mid_block2", L.mid_ch});
-        for (auto& u : L.up) blocks.push_back({u.name, u.cout});
-        HIP_OK(hipMemsetAsync(T.gta, 0, (size_t)pad16(c->max_batch) * Tm * sizeof(float), s));
-        int off = 0;
-        for (auto& bl : blocks) {
-            const int pw = c->pindex.at(bl.first + ".Dense_0.weight"), pb = c->pindex.at(bl.first + ".Dense_0.bias");
-            SgemmArgs g{};   // dWd[co][k] = sum_n gdense[n][off+co] * silu(temb[n][k])
-            g.A = T.gdense + off; g.a_m = 1; g.a_k = DT; g.a_act = 0;
-            g.B = c->d_temb; g.b_k = Tm; g.b_n = 1; g.b_act = 1;
-            g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1; g.accumulate = 0; g.M = bl.second; g.N = Tm; g.K = NB;
-            GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gdense + off, pgrad(pb), bl.second, 0});
-            SgemmArgs h{};   // gta[n][k] += sum_co gdense[n][off+co] * Wd[co][k]   (gta zeroed above; the 17 blocks add with atomics)
-            h.A = T.gdense + off; h.a_m = DT; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1;
-            h.C = T.gta; h.c_m = Tm; h.c_n = 1; h.accumulate = 1; h.M = NB; h.N = Tm; h.K = bl.second; h.no_split = 1;
-            GJ.push_back(h);
-            off += bl.second;
-        }
-        if (int e = flush_gemm()) return e;
-        if (int e = flush_col(NB, DT)) return e;
-        hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gta, (const float*)c->d_temb, (long)NB * Tm);
-        // gta is now g(temb)
-        if (c->arch.conditional) {
-            const int pw = c->pindex.at("label_emb.weight"), pb = c->pindex.at("label_emb.bias"), nc = c->arch.num_classes;
-            SgemmArgs g{};   // dWl[k][cl] = sum_n gtemb[n][k] * labels[n][cl]
-            g.A = T.gta; g.a_m = 1; g.a_k = Tm; g.B = T.lab_copy; g.b_k = nc; g.b_n = 1; g.C = pgrad(pw); g.c_m = nc; g.c_n = 1;
-            g.M = Tm; g.N = nc; g.K = NB;
-            GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gta, pgrad(pb), Tm, 0});
-        }
-        {
-            const int pw = c->pindex.at("time_mlp.2.weight"), pb = c->pindex.at("time_mlp.2.bias");
-            SgemmArgs g{};   // dW2[k][j] = sum_n gtemb[n][k] * silu(h1[n][j])
-            g.A = T.gta; g.a_m = 1; g.a_k = Tm; g.B = c->d_h1; g.b_k = Tm; g.b_n = 1; g.b_act = 1; g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1;
-            g.M = Tm; g.N = Tm; g.K = NB;
-            GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gta, pgrad(pb), Tm, 0});
-            SgemmArgs h{};   // gh1[n][j] = sum_k gtemb[n][k] * W2[k][j]
-            h.A = T.gta; h.a_m = Tm; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1; h.C = T.gh1; h.c_m = Tm; h.c_n = 1;
-            h.M = NB; h.N = Tm; h.K = Tm; h.no_split = 1;
-            GJ.push_back(h);
-            if (int e = flush_gemm()) return e;
-            if (int e = flush_col(NB, Tm)) return e;
-            hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gh1, (const float*)c->d_h1, (long)NB * Tm);
-        }
-        {
-            const int pw = c->pindex.at("time_mlp.0.weight"), pb = c->pindex.at("time_mlp.0.bias");
-            hipLaunchKernelGGL(fourier_kernel, dim3((unsigned)ceil_div(NB * 2 * nf, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)T.sig_copy,
-                               c->params[(size_t)c->pindex.at("time_embed.W")].ptr, T.four, NB, nf);
-            SgemmArgs g{};   // dW0[j][f] = sum_n gh1[n][j] * four[n][f]
-            g.A = T.gh1; g.a_m = 1; g.a_k = Tm; g.B = T.four; g.b_k = 2 * nf; g.b_n = 1; g.C = pgrad(pw); g.c_m = 2 * nf; g.c_n = 1;
-            g.M = Tm; g.N = 2 * nf; g.K = NB;
-            GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gh1, pgrad(pb), Tm, 0});
-            if (int e = flush_gemm()) return e;
-            if (int e = flush_col(NB, Tm)) return e;
-        }
-        HIP_OK(hipGetLastError());
-    }
+    if (int e = embed_backward(c, T, grads_flat, NB, s)) return e;
     if (T.two_streams)                                      // join: the caller's stream continues after the last weight gradients
         for (int p = 0; p < 2; ++p) if (done_rec[p]) HIP_OK(hipStreamWaitEvent(s, T.ev_done[p], 0));
     return 0;

@@ -213,8 +213,13 @@ class NCSNpp(nn.Module):
         return cache[1]
 
     def train_context(self, model_batch, H, W, device):
-        """A dedicated rdmi_ctx for training (layer plan, per-tensor activation storage, gradient workspace)."""
+        """A dedicated rdmi_ctx for training (layer plan, per-tensor activation storage, gradient workspace; shapes beyond
+        96 pixels or one channel: the tiled plan's fp32 backward, csrc/tiled_train.h)."""
         device = torch.device(device)
+        tiled = H * W > 96 or self.channels != 1            # the planner's rule (csrc/rdmi.hip build_plan)
+        if tiled and self.train_dtype == 'bf16':
+            raise NotImplementedError(f"train_dtype='bf16' is not built for the tiled plan ({self.channels}x{H}x{W} input): train this shape "
+                                      "with train_dtype='f32'")
         key = ('train', str(device), H, W)
         ctx = self._ctx.get(key)
         if ctx is None or ctx.max_batch < model_batch or ctx.train_dtype != self.train_dtype:
@@ -223,6 +228,8 @@ class NCSNpp(nn.Module):
             arch = self._arch()
             if self.train_dtype == 'bf16':
                 arch.compute_dtype = 1
+            elif tiled:
+                arch.compute_dtype = 0                        # the tiled training step is fp32 whatever compute_dtype the sampler uses
             ctx = _native.Context(arch, max(model_batch, 16), H, W, device)
             ctx.enable_training()
             ctx.train_dtype = self.train_dtype
