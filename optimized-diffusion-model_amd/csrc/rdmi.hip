@@ -13,6 +13,7 @@
 #include <cstring>
 #include <climits>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -46,6 +47,29 @@ int fail(const char* fmt, ...) {
         hipError_t e_ = (expr);                                                                  \
         if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// Owning handles of device memory (and of pinned host memory).  Kernel argument structs keep raw pointers: they are views,
+// filled with .get().  Only raw pointers reach hipLaunchKernelGGL.
+struct hip_free { void operator()(void* p) const { (void)hipFree(p); } };
+struct hip_host_free { void operator()(void* p) const { (void)hipHostFree(p); } };
+template <class T> using dev_ptr = std::unique_ptr<T, hip_free>;
+template <class T> using pinned_ptr = std::unique_ptr<T, hip_host_free>;
+
+// p = n fresh elements (what p held is released first); used as HIP_OK(hip_alloc(p, n))
+template <class T> hipError_t hip_alloc(dev_ptr<T>& p, size_t n) {
+    p.reset();
+    T* q = nullptr;
+    const hipError_t e = hipMalloc((void**)&q, n * sizeof(T));
+    if (e == hipSuccess) p.reset(q);
+    return e;
+}
+template <class T> hipError_t hip_alloc(pinned_ptr<T>& p, size_t n) {
+    p.reset();
+    T* q = nullptr;
+    const hipError_t e = hipHostMalloc((void**)&q, n * sizeof(T), 0);
+    if (e == hipSuccess) p.reset(q);
+    return e;
+}
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int pad16(int a) { return (a + 15) & ~15; }
@@ -113,6 +137,7 @@ struct Op {
 };
 
 struct ProfEntry { std::string name; double ms = 0; long launches = 0; double flops = 0; };
+struct TrainPlan;                        // csrc/train_plan.h
 
 }  // namespace
 
@@ -127,41 +152,32 @@ struct rdmi_ctx {
     std::vector<PackJob> jobs;          // host copy (src pointers patched from params before upload)
     std::vector<int> job_param;         // param index feeding each job
     std::vector<int> job_param2;        // second source of a job (PackJob::src2), -1: none; filled up to jobs.size() in do_repack
-    PackJob* d_jobs = nullptr;
-    float* d_w = nullptr;               // packed weight arena
+    dev_ptr<PackJob> d_jobs;
+    dev_ptr<float> d_w;                 // packed weight arena
     size_t w_floats = 0;
-    int* d_int = nullptr;               // tables and pixel maps
-    float* ws = nullptr;                // activation workspace
+    dev_ptr<int> d_int;                 // tables and pixel maps
+    dev_ptr<float> ws;                  // activation workspace
     size_t ws_per_sample = 0;
     // embedding path
     size_t w_t0 = 0, w_t2 = 0, w_dense = 0, b_dense = 0;
-    float *d_h1 = nullptr, *d_temb = nullptr, *d_dense = nullptr;
+    dev_ptr<float> d_h1, d_temb, d_dense;
     // sampler scratch
-    float *d_s2 = nullptr, *d_score = nullptr, *d_z = nullptr, *d_norms = nullptr, *d_ts = nullptr, *d_tvec = nullptr;
-    float *d_tt = nullptr, *d_th1 = nullptr; int tt_cap = 0;   // sampler: time-path rows of all updates (rdmi_pc_sample)
-    float* d_dense_all = nullptr; size_t dense_all_cap = 0;    // sampler: Dense_0 outputs of a chunk of updates [U][NBm][dense_total]
-    int ts_cap = 0;
-    StepState* d_state = nullptr;
-    // fused (workgroup-resident) path
-    bool fused_ok = false, use_fused = true;
-    std::string fused_why;               // why the fused program could not be built (falls back to the layer plan)
-    std::vector<FOp> fprog;              // host copy; parameter pointers are patched at repack time
+    dev_ptr<float> d_s2, d_score, d_z, d_norms, d_ts, d_tvec;
+    dev_ptr<float> d_tt, d_th1; int tt_cap = 0;                 // sampler: time-path rows of all updates (rdmi_pc_sample)
+    dev_ptr<float> d_dense_all; size_t dense_all_cap = 0;      // sampler: Dense_0 outputs of a chunk of updates [U][NBm][dense_total]
+    dev_ptr<StepState> d_state;
+    // fused (workgroup-resident) path: one program per samples-per-workgroup value
+    bool use_fused = true;
+    dev_ptr<long long> d_stamps;         // diagnostic (RDMI_STAMPS=1), shared by the programs that record stamps
     struct FPatch { int op; int field; std::string param; size_t arena_off; };
-    std::vector<FPatch> fpatch;
-    std::vector<short> ftabs;
-    FOp* d_fprog = nullptr; short* d_ftabs = nullptr;
-    float* d_spill = nullptr; size_t spill_per_sample = 0;
-    UnetArgs fargs{};
-    long long* d_stamps = nullptr;       // diagnostic (RDMI_STAMPS=1)
-    std::vector<std::string> fdesc;      // one line per fused op
-    size_t fused_lds = 0;
-    // (the fields above are the CONSTRUCTION state of one program; finished programs live here, one per samples-per-workgroup)
     struct FusedProg {
-        int S = 1; bool ok = false; std::string why;
-        std::vector<FOp> fprog; std::vector<FPatch> fpatch; std::vector<short> ftabs; std::vector<std::string> fdesc;
-        FOp* d_fprog = nullptr; short* d_ftabs = nullptr; float* d_spill = nullptr; size_t spill_per_sample = 0;
+        int S = 1; bool ok = false; std::string why;     // why: the reason the program could not be built (the layer plan runs instead)
+        std::vector<FOp> fprog;              // host copy; parameter pointers are patched at repack time
+        std::vector<FPatch> fpatch; std::vector<short> ftabs;
+        std::vector<std::string> fdesc;      // one line per fused op
+        dev_ptr<FOp> d_fprog; dev_ptr<short> d_ftabs; dev_ptr<float> d_spill; size_t spill_per_sample = 0;
         UnetArgs fargs{}; size_t fused_lds = 0;
-        bool coop = false; int n_xchg = 0; unsigned long long* d_xbuf = nullptr; int* d_coop_err = nullptr; int max_nb = 0;     // co-operative program
+        bool coop = false; int n_xchg = 0; dev_ptr<unsigned long long> d_xbuf; dev_ptr<int> d_coop_err; int max_nb = 0;     // co-operative program
         bool train = false;                  // the training forward's program (stashes every layer output, applies Dropout_0): never picked for inference
     };
     // tiled plan (shapes whose samples do not fit one workgroup: csrc/tiled_kernels.h)
@@ -188,12 +204,12 @@ struct rdmi_ctx {
     };
     bool tiled = false;
     bool in_train_forward = false;       // set around run_forward by rdmi_train_forward
-    bf16_t* d_w16 = nullptr;             // bf16 copies of the forward conv weights (training with compute_dtype = bf16)
+    dev_ptr<bf16_t> d_w16;               // bf16 copies of the forward conv weights (training with compute_dtype = bf16)
     std::vector<TLaunch> tl;
-    float *t_ws = nullptr, *t_xin = nullptr, *t_out = nullptr; size_t t_ws_per_sample = 0;
+    dev_ptr<float> t_ws, t_xin, t_out; size_t t_ws_per_sample = 0;
     long tiled_min_wgs = 512;                           // a tiled conv widens its workgroups (NCT column tiles per wave) while the launch keeps this many (RDMI_TILED_MIN_WGS: tests)
     long iconv_min_wgs = LONG_MAX;                      // iconv_kernel from this many 128 x 128 tiles per launch (off unless RDMI_ICONV=1 / RDMI_ICONV_MIN_WGS)
-    void* t_zero = nullptr;                             // 256 zero bytes: iconv_kernel's source for window pixels outside the image
+    dev_ptr<unsigned char> t_zero;                      // 256 zero bytes: iconv_kernel's source for window pixels outside the image
     std::vector<FusedProg> progs;
     int s_min_wg = 256;                            // a program with S samples per workgroup is used from batch s_min_wg * S (RDMI_S_MIN_WG: tests)
     bool use_coop = true;                          // RDMI_COOP=0: never select the co-operative program (A/B, tests)
@@ -215,8 +231,6 @@ struct rdmi_ctx {
     bool fused_ready() const { return !progs.empty() && progs[0].ok; }
     float train_drop_p = 0.f; const unsigned long long* train_seed_dev = nullptr;      // set around the training forward's launch
     int train_prog = -1;                           // index in progs of the training forward's program (-1: the layer plan runs the training forward)
-    int cur_train = 0;
-    int cur_coop = 0, cur_nxchg = 0, cur_cap_n = 0; unsigned long long* cur_xbuf = nullptr; int* cur_coop_err = nullptr;      // construction state (see stash_program)
     std::map<std::string, size_t> wmap;  // packed-weight arena offsets by parameter prefix
     bool packed_valid = false;
     bool debug_taps = false;
@@ -225,6 +239,8 @@ struct rdmi_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     std::vector<int> ev_entry;
     size_t ev_used = 0;
+    std::unique_ptr<TrainPlan> train;    // rdmi_enable_training (csrc/train_plan.h)
+    ~rdmi_ctx();                         // defined after train_plan.h: TrainPlan is complete there
 };
 
 namespace {
@@ -815,18 +831,18 @@ int build_tiled_plan(rdmi_ctx* c, Builder& b, const Layout& L, std::map<std::str
 // resolve a per-sample workspace offset to a device pointer (tensors are [tensor][n][...]: the offset scales with max_batch)
 inline float* tl_ptr(rdmi_ctx* c, size_t off, long delta = 0) {
     if (off == rdmi_ctx::TLaunch::NONE) return nullptr;
-    if (off == rdmi_ctx::TLaunch::XIN) return c->t_xin;
-    return c->t_ws + off * (size_t)c->max_batch + delta;
+    if (off == rdmi_ctx::TLaunch::XIN) return c->t_xin.get();
+    return c->t_ws.get() + off * (size_t)c->max_batch + delta;
 }
 
 int finish_tiled_plan(rdmi_ctx* c) {
     const size_t NBmax = (size_t)c->max_batch;
     const size_t E = (size_t)c->H * c->W * c->arch.channels;
-    HIP_OK(hipMalloc((void**)&c->t_ws, c->t_ws_per_sample * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->t_xin, E * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->t_out, E * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc(&c->t_zero, 256));
-    HIP_OK(hipMemset(c->t_zero, 0, 256));
+    HIP_OK(hip_alloc(c->t_ws, c->t_ws_per_sample * NBmax));
+    HIP_OK(hip_alloc(c->t_xin, E * NBmax));
+    HIP_OK(hip_alloc(c->t_out, E * NBmax));
+    HIP_OK(hip_alloc(c->t_zero, 256));
+    HIP_OK(hipMemset(c->t_zero.get(), 0, 256));
     // measured on MI355X (rocprofv3 kernel trace, B = 64 with guidance): 5.28 ms for the 3x3 convs of the 32x32 / 16x16 levels against 4.88 ms
     // with tconv_pre_kernel -- the implicit-GEMM form is NOT the default; RDMI_ICONV=1 selects it (from RDMI_ICONV_MIN_WGS tiles, default 256)
     if (const char* e = std::getenv("RDMI_TILED_MIN_WGS")) c->tiled_min_wgs = std::atol(e);
@@ -837,11 +853,11 @@ int finish_tiled_plan(rdmi_ctx* c) {
         if (l.kind == 0) {
             TConvArgs& a = l.conv;
             a.srcA = tl_ptr(c, l.oA); a.srcB = tl_ptr(c, l.oB); a.stats = tl_ptr(c, l.oStats); a.resid = tl_ptr(c, l.oResid);
-            a.out = l.out_is_final ? c->t_out : tl_ptr(c, l.oOut);
-            a.wpk = c->d_w + l.w_off;
-            a.dense = l.use_dense ? c->d_dense : nullptr;
+            a.out = l.out_is_final ? c->t_out.get() : tl_ptr(c, l.oOut);
+            a.wpk = c->d_w.get() + l.w_off;
+            a.dense = l.use_dense ? c->d_dense.get() : nullptr;
             a.chsum = tl_ptr(c, l.oC);
-            a.zeros = c->t_zero;
+            a.zeros = c->t_zero.get();
             if (l.pre && tconv_trv(a) * tconv_wl(a) * (a.ntap == 1 ? TpCfg<1>::UPP : TpCfg<9>::UPP) > TC_MAXS * RDMI_THREADS)
                 return fail("tiled conv %s: window of %d pixels exceeds the register staging", l.name.c_str(), tconv_trv(a) * tconv_wl(a));
             if (l.pre && tconv_pre_lds_bytes(a) > 160 * 1024) return fail("tiled conv %s: LDS window %zu B", l.name.c_str(), tconv_pre_lds_bytes(a));
@@ -873,6 +889,28 @@ int finish_tiled_plan(rdmi_ctx* c) {
 int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_mod, int sig_is_time, float t_scalar, float smin, float ratio, float* out, int NB,
               const float* dense_rows, hipStream_t s);
 int build_fused_program(rdmi_ctx* c);
+
+// the device buffers both plans share: weight arena (wf floats, zeroed), pack-job table, embedding rows, sampler scratch
+int alloc_arenas(rdmi_ctx* c, size_t wf) {
+    const size_t NBm = (size_t)c->max_batch, Mp = (size_t)pad16(c->max_batch), T = (size_t)c->temb;
+    const size_t E = (size_t)c->H * c->W * c->arch.channels;
+    c->w_floats = wf;
+    HIP_OK(hip_alloc(c->d_w, wf));
+    HIP_OK(hipMemset(c->d_w.get(), 0, wf * sizeof(float)));
+    HIP_OK(hip_alloc(c->d_jobs, c->jobs.size()));
+    HIP_OK(hip_alloc(c->d_h1, Mp * T));
+    HIP_OK(hip_alloc(c->d_temb, Mp * T));
+    HIP_OK(hip_alloc(c->d_dense, Mp * c->dense_total));
+    HIP_OK(hip_alloc(c->d_s2, NBm * E));
+    HIP_OK(hip_alloc(c->d_score, NBm * E));
+    HIP_OK(hip_alloc(c->d_z, NBm * E));
+    HIP_OK(hip_alloc(c->d_norms, 2 * NBm + 2));
+    HIP_OK(hip_alloc(c->d_tvec, NBm));
+    HIP_OK(hip_alloc(c->d_state, 1));
+    HIP_OK(hipMemset(c->d_state.get(), 0, sizeof(StepState)));
+    for (auto& j : c->jobs) j.dst = c->d_w.get() + reinterpret_cast<size_t>(j.dst);
+    return 0;
+}
 
 int build_plan(rdmi_ctx* c) {
     const rdmi_arch& a = c->arch;
@@ -910,22 +948,7 @@ int build_plan(rdmi_ctx* c) {
     if (c->H * c->W > 96 || a.channels != 1) {
         try { if (int e = build_tiled_plan(c, b, L, dense_off)) return e; }
         catch (const std::exception& ex) { return fail("tiled plan: %s", ex.what()); }
-        c->w_floats = b.wf;
-        HIP_OK(hipMalloc((void**)&c->d_w, c->w_floats * sizeof(float)));
-        HIP_OK(hipMemset(c->d_w, 0, c->w_floats * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_jobs, c->jobs.size() * sizeof(PackJob)));
-        const size_t NBm = (size_t)c->max_batch, Mp_ = (size_t)pad16(c->max_batch), E_ = (size_t)c->H * c->W * a.channels;
-        HIP_OK(hipMalloc((void**)&c->d_h1, Mp_ * T * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_temb, Mp_ * T * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_dense, Mp_ * dt * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_s2, NBm * E_ * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_score, NBm * E_ * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_z, NBm * E_ * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_norms, (2 * NBm + 2) * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_tvec, NBm * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_state, sizeof(StepState)));
-        HIP_OK(hipMemset(c->d_state, 0, sizeof(StepState)));
-        for (auto& j : c->jobs) j.dst = c->d_w + reinterpret_cast<size_t>(j.dst);
+        if (int e = alloc_arenas(c, b.wf)) return e;
         return finish_tiled_plan(c);
     }
     // ---- NCSNpp.forward data flow
@@ -1030,46 +1053,32 @@ int build_plan(rdmi_ctx* c) {
     }
 
     // ---- device allocations
-    c->w_floats = b.wf;
-    HIP_OK(hipMalloc((void**)&c->d_w, c->w_floats * sizeof(float)));
-    HIP_OK(hipMemset(c->d_w, 0, c->w_floats * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_int, std::max<size_t>(b.ints.size(), 1) * sizeof(int)));
-    HIP_OK(hipMemcpy(c->d_int, b.ints.data(), b.ints.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int e = alloc_arenas(c, b.wf)) return e;
+    HIP_OK(hip_alloc(c->d_int, std::max<size_t>(b.ints.size(), 1)));
+    HIP_OK(hipMemcpy(c->d_int.get(), b.ints.data(), b.ints.size() * sizeof(int), hipMemcpyHostToDevice));
     const size_t NBmax = (size_t)c->max_batch;
-    HIP_OK(hipMalloc((void**)&c->ws, c->ws_per_sample * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_jobs, c->jobs.size() * sizeof(PackJob)));
-    const size_t Mp = (size_t)pad16(c->max_batch);
-    HIP_OK(hipMalloc((void**)&c->d_h1, Mp * T * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_temb, Mp * T * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_dense, Mp * dt * sizeof(float)));
-    const size_t E = (size_t)c->H * c->W * a.channels;
-    HIP_OK(hipMalloc((void**)&c->d_s2, NBmax * E * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_score, NBmax * E * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_z, NBmax * E * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_norms, (2 * NBmax + 2) * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_tvec, NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_state, sizeof(StepState)));
-    HIP_OK(hipMemset(c->d_state, 0, sizeof(StepState)));
-    for (auto& j : c->jobs) j.dst = c->d_w + reinterpret_cast<size_t>(j.dst);
+    HIP_OK(hip_alloc(c->ws, c->ws_per_sample * NBmax));
 
     // ---- resolve pointers that do not depend on parameters
+    float* const w = c->d_w.get();
+    int* const ints = c->d_int.get();
     for (auto& op : c->ops) {
-        auto tptr = [&](int t) -> float* { return t >= 0 ? c->ws + c->tensors[(size_t)t].off * NBmax : nullptr; };
+        auto tptr = [&](int t) -> float* { return t >= 0 ? c->ws.get() + c->tensors[(size_t)t].off * NBmax : nullptr; };
         if (op.kind == OP_CONV) {
             ConvArgs& ca = op.conv;
             ca.srcA = tptr(op.tA); ca.srcB = tptr(op.tB); ca.scA = tptr(op.tScA); ca.scB = tptr(op.tScB);
             ca.resid = tptr(op.tRes);
             ca.out = tptr(op.out_tensor);
-            ca.tab = c->d_int + op.tab_off;
-            ca.mapA = op.has_mapA ? c->d_int + op.mapA_off : nullptr;
-            ca.mapSc = op.has_mapSc ? c->d_int + op.mapSc_off : nullptr;
-            ca.wpk = c->d_w + op.w_off;
-            ca.wsc = ca.Csc ? c->d_w + op.wsc_off : nullptr;
-            ca.dense = op.use_dense ? c->d_dense : nullptr;
+            ca.tab = ints + op.tab_off;
+            ca.mapA = op.has_mapA ? ints + op.mapA_off : nullptr;
+            ca.mapSc = op.has_mapSc ? ints + op.mapSc_off : nullptr;
+            ca.wpk = w + op.w_off;
+            ca.wsc = ca.Csc ? w + op.wsc_off : nullptr;
+            ca.dense = op.use_dense ? c->d_dense.get() : nullptr;
         } else {
             AttnArgs& aa = op.attn;
             aa.x = tptr(op.tA); aa.out = tptr(op.out_tensor);
-            aa.wqkv = c->d_w + op.w_off; aa.bqkv = c->d_w + op.bqkv_off; aa.w3 = c->d_w + op.w3_off;
+            aa.wqkv = w + op.w_off; aa.bqkv = w + op.bqkv_off; aa.w3 = w + op.w3_off;
         }
     }
     return build_fused_program(c);
@@ -1080,6 +1089,7 @@ int build_plan(rdmi_ctx* c) {
 // ------------------------------------------------------------------------------------------
 struct FusedBuilder {
     rdmi_ctx* c;
+    rdmi_ctx::FusedProg& prog;                 // the program being built
     static constexpr int LDS_TOTAL = 160 * 1024;
     struct Blk { int off, size; };
     std::vector<Blk> freel;
@@ -1123,7 +1133,7 @@ struct FusedBuilder {
         {
             std::string fl;
             for (auto& f : freel) fl += " [" + std::to_string(f.off) + "+" + std::to_string(f.size) + "]";
-            fail_("LDS arena exhausted at op " + std::to_string(c->fprog.size()) + " (need " + std::to_string(n) + " B; free:" + fl + ")");
+            fail_("LDS arena exhausted at op " + std::to_string(prog.fprog.size()) + " (need " + std::to_string(n) + " B; free:" + fl + ")");
         }
         return arena_lo;
     }
@@ -1158,7 +1168,7 @@ struct FusedBuilder {
         auto it = tabcache.find(key);
         if (it != tabcache.end()) return it->second;
         const int region = (S > 1 && cur_samp < 0) ? 1 : 0;
-        std::vector<short>& tb = region ? tabs1 : c->ftabs;
+        std::vector<short>& tb = region ? tabs1 : prog.ftabs;
         while (tb.size() % 2) tb.push_back(-1);
         const int off = (int)tb.size() | (region << 24);
         tb.insert(tb.end(), v.begin(), v.end());
@@ -1210,7 +1220,7 @@ struct FusedBuilder {
         o.kind = kind; o.a_off = -1; o.b_off = -1; o.a_map_off = -1; o.dense_off = -1; o.resid_off = -1; o.scale = 1.f; o.src_off = -1; o.gn_off = -1; o.samp = cur_samp; o.drop_op = -1;
         return o;
     }
-    int emit(const FOp& o) { flush_xchg(); c->fprog.push_back(o); return (int)c->fprog.size() - 1; }
+    int emit(const FOp& o) { flush_xchg(); prog.fprog.push_back(o); return (int)prog.fprog.size() - 1; }
     // all-gather of tensor t (column slices of 32 per member) between the four members; t2: a second tensor of the same shape
     int emit_xchg(const LT& t, const LT* own_rows_src) {
         FOp o = blank(FOP_XCHG);
@@ -1223,13 +1233,13 @@ struct FusedBuilder {
         }
         if (o.C < 32 || o.C > 128 || (o.C & (o.C - 1)) || o.rows * o.C > 512) fail_("exchange: block of " + std::to_string(o.rows) + " x " + std::to_string(o.C));
         xslot_granules = std::max(xslot_granules, 2 * o.rows * o.C);      // room for a second tensor (<= 1024 granules = 512 pairs: one per thread)
-        c->fprog.push_back(o);
-        return (int)c->fprog.size() - 1;
+        prog.fprog.push_back(o);
+        return (int)prog.fprog.size() - 1;
     }
     void flush_xchg() { if (pendx.on) { pendx.on = false; emit_xchg(pendx.t, nullptr); } }
     enum { F_GAMMA, F_BETA, F_BIAS, F_BIAS2, F_W, F_SC0W, F_SC1W, F_BIAS_ARENA };
-    void patch_param(int op, int field, const std::string& param) { c->fpatch.push_back({op, field, param, 0}); }
-    void patch_arena(int op, int field, size_t off) { c->fpatch.push_back({op, field, "", off}); }
+    void patch_param(int op, int field, const std::string& param) { prog.fpatch.push_back({op, field, param, 0}); }
+    void patch_arena(int op, int field, size_t off) { prog.fpatch.push_back({op, field, "", off}); }
 
     void gather_x(const LT& dst) {               // network input -> LDS [HW][16+4]
         FOp o = blank(FOP_GATHER);
@@ -1282,11 +1292,11 @@ struct FusedBuilder {
     bool try_fuse_gn(const LT& t, const std::string& pre, bool act, const LT* src) {
         if (!gn_fuse) return false;
         const LT& in = src ? *src : t;
-        int j = (int)c->fprog.size() - 1, jx = -1;
-        while (j >= 0 && (c->fprog[(size_t)j].kind == FOP_STORE || c->fprog[(size_t)j].kind == FOP_XCHG)) { if (c->fprog[(size_t)j].kind == FOP_XCHG) jx = j; --j; }
+        int j = (int)prog.fprog.size() - 1, jx = -1;
+        while (j >= 0 && (prog.fprog[(size_t)j].kind == FOP_STORE || prog.fprog[(size_t)j].kind == FOP_XCHG)) { if (prog.fprog[(size_t)j].kind == FOP_XCHG) jx = j; --j; }
         if (j < 0) return false;
-        FOp& p = c->fprog[(size_t)j];
-        if (p.coop && !pendx.on && (jx < 0 || c->fprog[(size_t)jx].dst_off != in.off || c->fprog[(size_t)jx].src_off >= 0)) return false;
+        FOp& p = prog.fprog[(size_t)j];
+        if (p.coop && !pendx.on && (jx < 0 || prog.fprog[(size_t)jx].dst_off != in.off || prog.fprog[(size_t)jx].src_off >= 0)) return false;
         if (p.kind != FOP_CONV || p.dst_kind != 0 || p.gn_off >= 0 || p.dst_off != in.off || p.dst_rs != in.rs) return false;
         if (p.Cout != t.C || p.rows != t.rows() || t.C % 4 != 0 || std::min(t.C / 4, 32) * 4 != t.C) return false;      // Cg == 4 only
         const int ntiles = p.Cout_pad >> 4;
@@ -1308,9 +1318,9 @@ struct FusedBuilder {
         }
         if (p.coop) {        // the conv now also produces the activated tensor (own columns): it has to travel too
             if (pendx.on) {
-                if (src) { pendx.on = false; const int ix = emit_xchg(in, nullptr); c->fprog[(size_t)ix].src_off = t.off; c->fprog[(size_t)ix].src_rs = t.rs; }
+                if (src) { pendx.on = false; const int ix = emit_xchg(in, nullptr); prog.fprog[(size_t)ix].src_off = t.off; prog.fprog[(size_t)ix].src_rs = t.rs; }
                 // in-place form: the pending exchange of the conv's destination already carries the activated values
-            } else if (src) { c->fprog[(size_t)jx].src_off = t.off; c->fprog[(size_t)jx].src_rs = t.rs; }
+            } else if (src) { prog.fprog[(size_t)jx].src_off = t.off; prog.fprog[(size_t)jx].src_rs = t.rs; }
         }
         return true;
     }
@@ -1379,16 +1389,16 @@ struct FusedBuilder {
                 if (it == lp_tensor.end()) fail_("training forward: no layer-plan tensor '" + tn + "'");
                 else {
                     const Tensor& t = c->tensors[(size_t)it->second];
-                    FOp& q = c->fprog[(size_t)idx];
+                    FOp& q = prog.fprog[(size_t)idx];
                     if (t.C != Cout || t.H * t.W != q.rows) fail_("training forward: tensor '" + tn + "' has another shape");
-                    q.stash = c->ws + t.off * (size_t)c->max_batch;
+                    q.stash = c->ws.get() + t.off * (size_t)c->max_batch;
                     q.stash_bf16 = c->arch.compute_dtype == 1 ? 1 : 0;
                 }
             }
-            c->fprog[(size_t)idx].drop_op = -1;
+            prog.fprog[(size_t)idx].drop_op = -1;
         }
         if (coop && cur_samp < 0) {      // low-resolution section of the co-operative program: column-sliced, K split over the waves
-            FOp& q = c->fprog[(size_t)idx];
+            FOp& q = prog.fprog[(size_t)idx];
             q.coop = 1;
             if (q.Cout_pad != 128 || q.mtiles != 1 || q.main_ph.nch % 4 != 0 || dst_kind != 0 || !dst || dst->C != 128)
                 fail_("co-operative conv shape (Cout " + std::to_string(Cout) + ", " + std::to_string(q.mtiles) + " row tiles, " + std::to_string(q.main_ph.nch) + " chunks)");
@@ -1452,7 +1462,7 @@ FusedBuilder::LT fused_attn(FusedBuilder& b, const std::string& name, FusedBuild
     {   // q, k, v in one contraction: the layer plan already packs NIN_0..2 side by side? no: [3][C/16][C][16] -> use the
         // dedicated fused packing [C/16][3C][16] (wmap key ".qkv3")
         const int idx = b.conv(xn, H, W, H, W, 1, 0, 1, name + (fold3 ? ".qkv3f" : ".qkv3"), 0, 3 * C, "", bq, 3, &q, 1.f, -1, nullptr, nullptr, "", "");
-        FOp& o = c->fprog[(size_t)idx];
+        FOp& o = b.prog.fprog[(size_t)idx];
         o.dst2_off = k.off; o.dst3_off = vt_off; o.dst3_rs = ps; o.split_C = C;
         o.qkv1 = (std::getenv("RDMI_NO_QKV1") == nullptr && o.ntap == 1 && o.main_ph.nch == 4 && o.Cout_pad == 192 && C == 64 && o.mtiles <= 6) ? 1 : 0;
     }
@@ -1478,33 +1488,18 @@ FusedBuilder::LT fused_attn(FusedBuilder& b, const std::string& name, FusedBuild
     return out;
 }
 
-int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESERVE, int* tab_used, int* tab1_used, bool coop, bool train);
+int build_fused_program_pass(rdmi_ctx* c, rdmi_ctx::FusedProg& q, int S, int TAB_RESERVE, int TAB1_RESERVE, int* tab_used, int* tab1_used, bool coop, bool train);
 
-// A built program is moved out of the context's construction fields into one of these (one per samples-per-workgroup value).
-void stash_program(rdmi_ctx* c, int S) {
-    rdmi_ctx::FusedProg q;
-    q.S = S; q.ok = c->fused_ok; q.why = c->fused_why;
-    q.fprog.swap(c->fprog); q.fpatch.swap(c->fpatch); q.ftabs.swap(c->ftabs); q.fdesc.swap(c->fdesc);
-    q.d_fprog = c->d_fprog; q.d_ftabs = c->d_ftabs; q.d_spill = c->d_spill; q.spill_per_sample = c->spill_per_sample;
-    q.fargs = c->fargs; q.fused_lds = c->fused_lds;
-    q.train = c->cur_train != 0; c->cur_train = 0;
-    q.coop = c->cur_coop != 0; q.n_xchg = c->cur_nxchg; q.d_xbuf = c->cur_xbuf; q.d_coop_err = c->cur_coop_err; q.max_nb = c->cur_cap_n;
-    c->cur_coop = 0; c->cur_nxchg = 0; c->cur_xbuf = nullptr; c->cur_coop_err = nullptr; c->cur_cap_n = 0;
-    c->d_fprog = nullptr; c->d_ftabs = nullptr; c->d_spill = nullptr; c->spill_per_sample = 0; c->fused_ok = false; c->fused_why.clear();
-    c->progs.push_back(std::move(q));
-}
-
+// Two passes: the first sizes the row-table regions (and is dropped), the second builds the program with them sized exactly.
 int build_one_program(rdmi_ctx* c, int S, bool coop = false, bool train = false) {
     int used = 0, used1 = 0;
-    if (int e = build_fused_program_pass(c, S, 8 * 1024, 24 * 1024, &used, &used1, coop, train)) return e;
-    if (c->fused_ok) {   // second pass with the table region sized exactly
-        for (void* p : {(void*)c->d_fprog, (void*)c->d_ftabs, (void*)c->d_spill, (void*)c->cur_xbuf, (void*)c->cur_coop_err}) if (p) (void)hipFree(p);
-        c->d_fprog = nullptr; c->d_ftabs = nullptr; c->d_spill = nullptr; c->cur_xbuf = nullptr; c->cur_coop_err = nullptr;
+    {
+        rdmi_ctx::FusedProg sizing;
+        if (int e = build_fused_program_pass(c, sizing, S, 8 * 1024, 24 * 1024, &used, &used1, coop, train)) return e;
     }
-    c->fused_ok = false; c->fprog.clear(); c->fpatch.clear(); c->ftabs.clear(); c->fused_why.clear();
-    if (int e = build_fused_program_pass(c, S, (used + 63) & ~63, (used1 + 63) & ~63, &used, &used1, coop, train)) return e;
-    c->cur_train = train ? 1 : 0;
-    stash_program(c, S);
+    rdmi_ctx::FusedProg q;
+    if (int e = build_fused_program_pass(c, q, S, (used + 63) & ~63, (used1 + 63) & ~63, &used, &used1, coop, train)) return e;
+    c->progs.push_back(std::move(q));
     return 0;
 }
 
@@ -1541,10 +1536,11 @@ int build_fused_program(rdmi_ctx* c) {
     return 0;
 }
 
-int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESERVE, int* tab_used, int* tab1_used, bool coop, bool train) {
+int build_fused_program_pass(rdmi_ctx* c, rdmi_ctx::FusedProg& q, int S, int TAB_RESERVE, int TAB1_RESERVE, int* tab_used, int* tab1_used, bool coop, bool train) {
     using LT = FusedBuilder::LT;
     const rdmi_arch& a = c->arch;
-    FusedBuilder b{c};
+    q.S = S; q.train = train;
+    FusedBuilder b{c, q};
     b.S = S; b.coop = coop; b.train = train;
     if (train) {
         for (size_t i = 0; i < c->tensors.size(); ++i) b.lp_tensor[c->tensors[i].name] = (int)i;
@@ -1567,7 +1563,7 @@ int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESER
     b.gn_slot_off = TAB_RESERVE + zero_bytes;
     b.gn_fuse = std::getenv("RDMI_NO_GNFUSE") == nullptr;
     const int H0 = c->H, W0 = c->W;
-    if (H0 * W0 > 96) { c->fused_why = "more than 96 pixels per sample"; return 0; }
+    if (H0 * W0 > 96) { q.why = "more than 96 pixels per sample"; return 0; }
     const int nlev = a.n_levels;
     const bool multi = S > 1;
 
@@ -1629,7 +1625,7 @@ int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESER
             b.multi_slot_off = -1;
             b.free_bytes(b.tab1_lds, TAB1_RESERVE);
             while (b.tabs1.size() % 8) b.tabs1.push_back(-1);
-            c->fprog[(size_t)loadtab_op].rows = (int)b.tabs1.size() * 2;      // bytes
+            q.fprog[(size_t)loadtab_op].rows = (int)b.tabs1.size() * 2;      // bytes
         };
         auto enter_coop = [&]() {                     // h: this member's own sample -> the four samples of the group (rows of sample m come from member m)
             b.flush_xchg();
@@ -1645,7 +1641,7 @@ int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESER
             b.cur_samp = 0;
             LT own = b.talloc(ch, H, W);
             b.copy_t(own, h);
-            c->fprog.back().a_hw = own.hw(); c->fprog.back().a_mstride = own.hw() * h.rs * 4;
+            q.fprog.back().a_hw = own.hw(); q.fprog.back().a_mstride = own.hw() * h.rs * 4;
             b.tfree(h);
             h = own; in_coop = false;
             leave_multi();
@@ -1739,19 +1735,19 @@ int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESER
     }
     if (H != c->H || W != c->W) b.fail_("network output grid differs from the input grid");
 
-    *tab_used = (int)c->ftabs.size() * 2 + 16;
+    *tab_used = (int)q.ftabs.size() * 2 + 16;
     *tab1_used = (int)b.tabs1.size() * 2 + 16;
     if (*tab_used > TAB_RESERVE && TAB_RESERVE != 8 * 1024) b.fail_("row tables exceed the reserved LDS region");
     if (*tab1_used > TAB1_RESERVE && multi) b.fail_("low-resolution row tables exceed their LDS block");
     int cmax = 16;
-    for (auto& o : c->fprog) if (o.kind == FOP_CONV) { cmax = std::max(cmax, o.main_ph.nch * 16); for (int s2 = 0; s2 < o.nsc; ++s2) cmax = std::max(cmax, o.sc[s2].nch * 16); }
+    for (auto& o : q.fprog) if (o.kind == FOP_CONV) { cmax = std::max(cmax, o.main_ph.nch * 16); for (int s2 = 0; s2 < o.nsc; ++s2) cmax = std::max(cmax, o.sc[s2].nch * 16); }
     if (cmax * 4 + 64 > zero_bytes) b.fail_("zero row too small");
-    if (b.failed && TAB_RESERVE == 8 * 1024 && *tab_used <= 8 * 1024) { c->fprog.clear(); c->fpatch.clear(); c->ftabs.clear(); c->fused_ok = false; return 0; }   // pass 1 only sizes the tables
-    if (b.failed) { c->fused_why = b.why; c->fprog.clear(); c->fpatch.clear(); c->ftabs.clear(); return 0; }
+    if (b.failed && TAB_RESERVE == 8 * 1024 && *tab_used <= 8 * 1024) return 0;      // pass 1 only sizes the tables
+    if (b.failed) { q.why = b.why; return 0; }
 
     // table offsets (shorts, relative) -> LDS byte offsets
     auto tab_lds = [&](int ref) { return (ref >> 24) ? b.tab1_lds + (ref & 0xffffff) * 2 : (ref & 0xffffff) * 2; };
-    for (auto& o : c->fprog) {
+    for (auto& o : q.fprog) {
         if (o.kind == FOP_CONV) {
             for (int t = 0; t < o.ntap; ++t) o.tab_off[t] = tab_lds(o.tab_off[t]);
             for (int s2 = 0; s2 < o.nsc; ++s2) o.sc[s2].tab_off = tab_lds(o.sc[s2].tab_off);
@@ -1759,10 +1755,10 @@ int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESER
             o.a_map_off = tab_lds(o.a_map_off);
         }
     }
-    while (c->ftabs.size() % 8) c->ftabs.push_back(-1);
-    const size_t tab0_shorts = c->ftabs.size();                  // region 0 is what the kernel copies at start; region 1 follows it in the buffer
-    c->ftabs.insert(c->ftabs.end(), b.tabs1.begin(), b.tabs1.end());
-    c->spill_per_sample = b.spill_floats;
+    while (q.ftabs.size() % 8) q.ftabs.push_back(-1);
+    const size_t tab0_shorts = q.ftabs.size();                  // region 0 is what the kernel copies at start; region 1 follows it in the buffer
+    q.ftabs.insert(q.ftabs.end(), b.tabs1.begin(), b.tabs1.end());
+    q.spill_per_sample = b.spill_floats;
     // spill slots are [slot][n][rows][C].  Co-operative program: the low-resolution slots are indexed by (workgroup, sample of its group),
     // n = 4 * workgroup id + slot, so the buffer holds 4 * (largest grid) "samples" per slot
     int coop_max_nb = 0, spill_n = c->max_batch;
@@ -1774,52 +1770,53 @@ int build_fused_program_pass(rdmi_ctx* c, int S, int TAB_RESERVE, int TAB1_RESER
         const int grid_max = ceil_div(ceil_div(std::max(coop_max_nb, 1), 4), st) * 4 * st;
         spill_n = 4 * grid_max;
     }
-    if (b.failed) { c->fused_why = b.why; c->fprog.clear(); c->fpatch.clear(); c->ftabs.clear(); return 0; }
-    HIP_OK(hipMalloc((void**)&c->d_spill, std::max<size_t>(c->spill_per_sample, 1) * (size_t)spill_n * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->d_fprog, c->fprog.size() * sizeof(FOp)));
-    HIP_OK(hipMalloc((void**)&c->d_ftabs, c->ftabs.size() * sizeof(short)));
-    HIP_OK(hipMemcpy(c->d_ftabs, c->ftabs.data(), c->ftabs.size() * sizeof(short), hipMemcpyHostToDevice));
+    if (b.failed) { q.why = b.why; return 0; }
+    HIP_OK(hip_alloc(q.d_spill, std::max<size_t>(q.spill_per_sample, 1) * (size_t)spill_n));
+    HIP_OK(hip_alloc(q.d_fprog, q.fprog.size()));
+    HIP_OK(hip_alloc(q.d_ftabs, q.ftabs.size()));
+    HIP_OK(hipMemcpy(q.d_ftabs.get(), q.ftabs.data(), q.ftabs.size() * sizeof(short), hipMemcpyHostToDevice));
     // spill slots: [slot][n][rows][C] so a workgroup only ever touches its own sample's rows
     for (auto& f : b.spill_fix) {
-        FOp& o = c->fprog[(size_t)f.op];
-        float* p = c->d_spill + f.off * (size_t)spill_n;
+        FOp& o = q.fprog[(size_t)f.op];
+        float* p = q.d_spill.get() + f.off * (size_t)spill_n;
         if (f.which == 1) o.b_g = p; else if (f.which == 2) o.a_g = p; else o.g_out = p;
     }
-    c->fargs = UnetArgs{};
-    c->fargs.prog = c->d_fprog; c->fargs.nops = (int)c->fprog.size();
-    c->fargs.tabs = c->d_ftabs; c->fargs.tab_bytes = (int)(tab0_shorts * sizeof(short)); c->fargs.tab_base = 0;
-    if (loadtab_idx >= 0) c->fprog[(size_t)loadtab_idx].a_g = reinterpret_cast<const float*>(c->d_ftabs + tab0_shorts);
-    c->fargs.zero_off = TAB_RESERVE; c->fargs.zero_bytes = zero_bytes;
-    c->fargs.dense = c->d_dense; c->fargs.dense_stride = c->dense_total; c->fargs.S = S;
-    c->fargs.out_elems = c->H * c->W * a.channels;
+    UnetArgs& fa = q.fargs;
+    fa = UnetArgs{};
+    fa.prog = q.d_fprog.get(); fa.nops = (int)q.fprog.size();
+    fa.tabs = q.d_ftabs.get(); fa.tab_bytes = (int)(tab0_shorts * sizeof(short)); fa.tab_base = 0;
+    if (loadtab_idx >= 0) q.fprog[(size_t)loadtab_idx].a_g = reinterpret_cast<const float*>(q.d_ftabs.get() + tab0_shorts);
+    fa.zero_off = TAB_RESERVE; fa.zero_bytes = zero_bytes;
+    fa.dense = c->d_dense.get(); fa.dense_stride = c->dense_total; fa.S = S;
+    fa.out_elems = c->H * c->W * a.channels;
     if (coop) {
         const int groups_max = ceil_div(coop_max_nb, 4);
         const size_t xb = (size_t)groups_max * 2 * 4 * (size_t)b.xslot_granules * sizeof(unsigned long long);
-        HIP_OK(hipMalloc((void**)&c->cur_xbuf, std::max<size_t>(xb, 16)));
-        HIP_OK(hipMemset(c->cur_xbuf, 0, std::max<size_t>(xb, 16)));          // tags start at 0; epochs never are
-        HIP_OK(hipMalloc((void**)&c->cur_coop_err, 16));
-        HIP_OK(hipMemset(c->cur_coop_err, 0, 16));
-        c->fargs.coop = 1; c->fargs.coop_stride = c->coop_stride; c->fargs.xbuf = c->cur_xbuf; c->fargs.xslot = b.xslot_granules;
-        c->fargs.coop_err = c->cur_coop_err;
-        if (const char* e = std::getenv("RDMI_COOP_TEST_BREAK")) c->fargs.coop_break = atoi(e);
-        c->cur_coop = 1; c->cur_nxchg = b.n_xchg; c->cur_cap_n = coop_max_nb;
+        HIP_OK(hip_alloc(q.d_xbuf, std::max<size_t>(xb, 16) / sizeof(unsigned long long)));
+        HIP_OK(hipMemset(q.d_xbuf.get(), 0, std::max<size_t>(xb, 16)));          // tags start at 0; epochs never are
+        HIP_OK(hip_alloc(q.d_coop_err, 4));
+        HIP_OK(hipMemset(q.d_coop_err.get(), 0, 16));
+        fa.coop = 1; fa.coop_stride = c->coop_stride; fa.xbuf = q.d_xbuf.get(); fa.xslot = b.xslot_granules;
+        fa.coop_err = q.d_coop_err.get();
+        if (const char* e = std::getenv("RDMI_COOP_TEST_BREAK")) fa.coop_break = atoi(e);
+        q.coop = true; q.n_xchg = b.n_xchg; q.max_nb = coop_max_nb;
     }
-    c->fused_lds = (size_t)b.high_water;
-    if (const char* e = std::getenv("RDMI_UDBG")) c->fargs.dbg = atoi(e);
+    q.fused_lds = (size_t)b.high_water;
+    if (const char* e = std::getenv("RDMI_UDBG")) fa.dbg = atoi(e);
     if (std::getenv("RDMI_STAMPS") && (S == 1 || coop)) {       // diagnostic builds exist for the single-sample and the co-operative program
-        if (!c->d_stamps) HIP_OK(hipMalloc((void**)&c->d_stamps, (1024 + 200 * 8 + 8) * sizeof(long long)));
-        if (c->fprog.size() > 200) return fail("RDMI_STAMPS: program of %zu ops", c->fprog.size());
-        c->fargs.stamps = c->d_stamps;
+        if (!c->d_stamps) HIP_OK(hip_alloc(c->d_stamps, 1024 + 200 * 8 + 8));
+        if (q.fprog.size() > 200) return fail("RDMI_STAMPS: program of %zu ops", q.fprog.size());
+        fa.stamps = c->d_stamps.get();
     }
-    c->fdesc.clear();
-    for (auto& o : c->fprog) {
+    q.fdesc.clear();
+    for (auto& o : q.fprog) {
         char buf[160];
         const char* kn[] = {"GATHER", "STORE", "GN", "CONV", "ATTN", "LOADTAB", "XCHG"};
         if (o.kind == FOP_CONV) snprintf(buf, sizeof buf, "CONV rows=%d mtiles=%d K=%dx%d(+%d) Cout=%d dst=%d%s", o.rows, o.mtiles, o.ntap, o.main_ph.nch * 16, o.nsc ? o.sc[0].nch * 16 : 0, o.Cout, o.dst_kind, o.gn_off >= 0 ? (o.gn_raw ? (o.coop ? " +GN(copy) coop" : " +GN(copy)") : (o.coop ? " +GN coop" : " +GN")) : (o.coop ? " coop" : ""));
         else snprintf(buf, sizeof buf, "%s rows=%d C=%d", kn[o.kind], o.rows, o.C);
-        c->fdesc.push_back(buf);
+        q.fdesc.push_back(buf);
     }
-    c->fused_ok = true;
+    q.ok = true;
     return 0;
 }
 
@@ -1920,10 +1917,10 @@ int do_repack(rdmi_ctx* c, hipStream_t s) {
     }
     for (auto& p : c->params)
         if (!p.ptr) return fail("parameter '%s' was never bound (rdmi_set_param)", p.name.c_str());
-    HIP_OK(hipMemcpyAsync(c->d_jobs, c->jobs.data(), c->jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->d_jobs.get(), c->jobs.data(), c->jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
     {
         ProfScope ps(c, s, "pack_kernel", 0);
-        hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)c->jobs.size()), dim3(RDMI_THREADS), 0, s, (const PackJob*)c->d_jobs);
+        hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)c->jobs.size()), dim3(RDMI_THREADS), 0, s, (const PackJob*)c->d_jobs.get());
     }
     HIP_OK(hipGetLastError());
     // parameter-dependent pointers
@@ -1941,7 +1938,7 @@ int do_repack(rdmi_ctx* c, hipStream_t s) {
     for (auto& l : c->tl) {
         if (l.kind == 6) { l.gact.gamma = P(c, l.p_gamma); l.gact.beta = P(c, l.p_beta); continue; }
         if (l.kind != 0) continue;
-        l.conv.bias = l.p_bias.empty() ? c->d_w + l.bias_arena : P(c, l.p_bias);
+        l.conv.bias = l.p_bias.empty() ? c->d_w.get() + l.bias_arena : P(c, l.p_bias);
         l.conv.gamma = l.p_gamma.empty() ? nullptr : P(c, l.p_gamma);
         l.conv.beta = l.p_beta.empty() ? nullptr : P(c, l.p_beta);
     }
@@ -1949,7 +1946,7 @@ int do_repack(rdmi_ctx* c, hipStream_t s) {
         if (!q.ok) continue;
         for (auto& f : q.fpatch) {
             FOp& o = q.fprog[(size_t)f.op];
-            const float* p = f.param.empty() ? c->d_w + f.arena_off : P(c, f.param);
+            const float* p = f.param.empty() ? c->d_w.get() + f.arena_off : P(c, f.param);
             switch (f.field) {
                 case FusedBuilder::F_GAMMA: o.gamma = p; break;
                 case FusedBuilder::F_BETA: o.beta = p; break;
@@ -1960,7 +1957,7 @@ int do_repack(rdmi_ctx* c, hipStream_t s) {
                 case FusedBuilder::F_SC1W: o.sc[1].w = p; break;
             }
         }
-        HIP_OK(hipMemcpyAsync(q.d_fprog, q.fprog.data(), q.fprog.size() * sizeof(FOp), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(q.d_fprog.get(), q.fprog.data(), q.fprog.size() * sizeof(FOp), hipMemcpyHostToDevice, s));
     }
     if (c->fused_ready()) HIP_OK(hipStreamSynchronize(s));
     c->packed_valid = true;
@@ -1990,15 +1987,15 @@ int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
     l.M = f.NB; l.fourW = P(c, "time_embed.W"); l.nfour = a.nf;
     l.X = f.sig; l.x_mod = f.sig_mod > 0 ? f.sig_mod : f.NB; l.t_is_time = f.t_is_time; l.smin = f.smin; l.ratio = f.ratio;
     l.use_scalar = f.sig ? 0 : 1; l.t_scalar = f.t_scalar;
-    l.pre = 2; l.K = pad16(2 * a.nf); l.W = c->d_w + c->w_t0; l.Npad = Np_t; l.N = T; l.bias = P(c, "time_mlp.0.bias");
-    l.Y = c->d_h1; l.ldy = T;
+    l.pre = 2; l.K = pad16(2 * a.nf); l.W = c->d_w.get() + c->w_t0; l.Npad = Np_t; l.N = T; l.bias = P(c, "time_mlp.0.bias");
+    l.Y = c->d_h1.get(); l.ldy = T;
     {
         ProfScope ps(c, s, "linear_mfma(time_mlp.0)", 2.0 * f.NB * T * 2 * a.nf);
         hipLaunchKernelGGL(linear_mfma_kernel<1>, dim3((unsigned)ceil_div(f.NB, 16), (unsigned)(Np_t / 64)), dim3(RDMI_THREADS), 0, s, l);
     }
     LinArgs l2{};
-    l2.M = f.NB; l2.X = c->d_h1; l2.ldx = T; l2.pre = 1; l2.K = T; l2.W = c->d_w + c->w_t2; l2.Npad = Np_t; l2.N = T;
-    l2.bias = P(c, "time_mlp.2.bias"); l2.Y = c->d_temb; l2.ldy = T;
+    l2.M = f.NB; l2.X = c->d_h1.get(); l2.ldx = T; l2.pre = 1; l2.K = T; l2.W = c->d_w.get() + c->w_t2; l2.Npad = Np_t; l2.N = T;
+    l2.bias = P(c, "time_mlp.2.bias"); l2.Y = c->d_temb.get(); l2.ldy = T;
     if (a.conditional) { l2.labels = f.labels; l2.Wl = P(c, "label_emb.weight"); l2.bl = P(c, "label_emb.bias"); l2.ncls = a.num_classes; l2.label_rows = f.label_rows; }
     {
         ProfScope ps(c, s, "linear_mfma(time_mlp.2)", 2.0 * f.NB * T * T);
@@ -2007,12 +2004,12 @@ int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
     }
     if (!f.dense_rows) {
     LinArgs l3{};
-    l3.M = f.NB; l3.X = c->d_temb; l3.ldx = T; l3.pre = 1; l3.K = T;
+    l3.M = f.NB; l3.X = c->d_temb.get(); l3.ldx = T; l3.pre = 1; l3.K = T;
     if (f.tt_row) {     // every sample shares the time row; the label embedding is added in the prologue (same sums as time_mlp.2's epilogue)
         l3.X = f.tt_row; l3.ldx = 0; l3.pre = 3;
         if (a.conditional) { l3.labels = f.labels; l3.Wl = P(c, "label_emb.weight"); l3.ncls = a.num_classes; l3.label_rows = f.label_rows; }
-    } l3.W = c->d_w + c->w_dense; l3.Npad = Np_d; l3.N = c->dense_total;
-    l3.bias = c->d_w + c->b_dense; l3.Y = c->d_dense; l3.ldy = c->dense_total;
+    } l3.W = c->d_w.get() + c->w_dense; l3.Npad = Np_d; l3.N = c->dense_total;
+    l3.bias = c->d_w.get() + c->b_dense; l3.Y = c->d_dense.get(); l3.ldy = c->dense_total;
     {
         ProfScope ps(c, s, "linear_mfma(Dense_0 x all)", 2.0 * f.NB * T * c->dense_total);
         hipLaunchKernelGGL((linear_mfma_kernel<1, 16>), dim3((unsigned)ceil_div(f.NB, 16), (unsigned)(Np_d / 64)), dim3(RDMI_THREADS), 0, s, l3);
@@ -2094,7 +2091,7 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
     const rdmi_arch& a = c->arch;
     const int HW = c->H * c->W, Cc = a.channels;
     const long tot = (long)NB * HW * Cc;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, x, c->t_xin, NB, HW, Cc, x_mod);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, x, c->t_xin.get(), NB, HW, Cc, x_mod);
     for (auto& l : c->tl) {
         if (l.kind == 0) {
             TConvArgs ca = l.conv;
@@ -2197,7 +2194,7 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
             hipLaunchKernelGGL(transpose_lc_kernel, dim3((unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, l.tsrc, l.tdst, NB, l.tL, l.tC, l.tld, l.tc0);
         }
     }
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)c->t_out, out, NB, HW, Cc, 0);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)c->t_out.get(), out, NB, HW, Cc, 0);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -2206,6 +2203,25 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
 
 #include "train_plan.h"
 #include "tiled_train.h"
+
+// The non-memory handles of a training plan, in this order; its buffers (and the tiled part) are released with the members after.
+TrainPlan::~TrainPlan() {
+    if (side) (void)hipStreamSynchronize(side);
+    if (fwd_exec) (void)hipGraphExecDestroy(fwd_exec);
+    if (bwd_exec) (void)hipGraphExecDestroy(bwd_exec);
+    for (int p = 0; p < 2; ++p) {
+        if (ev_ready[p]) (void)hipEventDestroy(ev_ready[p]);
+        if (ev_done[p]) (void)hipEventDestroy(ev_done[p]);
+    }
+    if (side) (void)hipStreamDestroy(side);
+    if (cap) (void)hipStreamDestroy(cap);
+}
+
+// the training plan first (it synchronises its side stream), then the profiling events; the buffers go with the members
+rdmi_ctx::~rdmi_ctx() {
+    train.reset();
+    for (auto& ev : ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+}
 
 // ============================================================================================
 // C ABI
@@ -2219,12 +2235,12 @@ int rdmi_debug_op_cycles(rdmi_ctx* c, long long* host, int cap, const char** des
     const int n = (int)q0.fprog.size();
     std::vector<long long> st((size_t)n + 1);
     if (n > 1000) return 0;
-    if (hipMemcpy(st.data(), c->d_stamps, st.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (hipMemcpy(st.data(), c->d_stamps.get(), st.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     for (int i = 0; i < n && i < cap; ++i) host[i] = st[(size_t)i + 1] - st[(size_t)i];
     // fine stamps of CONV ops (entry, ring issued, first B landed, main done, shortcut done, epilogue done) follow at cap/2
     {
         std::vector<long long> fs((size_t)n * 8);
-        if (hipMemcpy(fs.data(), c->d_stamps + 1024, fs.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipMemcpy(fs.data(), c->d_stamps.get() + 1024, fs.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
             for (int i = 0; i < n && 256 + i * 8 + 7 < cap; ++i)
                 for (int k = 0; k < 8; ++k) host[256 + i * 8 + k] = fs[(size_t)i * 8 + k] - st[(size_t)i];
     }
@@ -2270,7 +2286,7 @@ int rdmi_coop_status(rdmi_ctx* c, int* gave_up) {
     if (!c || !gave_up) return fail("null argument");
     *gave_up = 0;
     for (auto& q : c->progs)
-        if (q.coop && q.d_coop_err) { int v = 0; HIP_OK(hipMemcpy(&v, q.d_coop_err, sizeof v, hipMemcpyDeviceToHost)); *gave_up |= v; }
+        if (q.coop && q.d_coop_err) { int v = 0; HIP_OK(hipMemcpy(&v, q.d_coop_err.get(), sizeof v, hipMemcpyDeviceToHost)); *gave_up |= v; }
     if (*gave_up) c->use_coop = false;       // the groups of this device were not co-resident once: later calls take the single-sample programs
     return 0;
 }
@@ -2295,38 +2311,12 @@ int rdmi_create(const rdmi_arch* arch, int max_batch, int H, int W, rdmi_ctx** o
     if (const char* e = std::getenv("RDMI_PATH")) c->use_fused = std::string(e) != "layers";
     int e = 0;
     try { e = build_plan(c); } catch (const std::exception& ex) { e = fail("plan construction failed: %s", ex.what()); }
-    if (e) { rdmi_destroy(c); return e; }
+    if (e) { delete c; return e; }
     *out = c;
     return 0;
 }
 
 int rdmi_destroy(rdmi_ctx* c) {
-    if (!c) return 0;
-    if (TrainPlan* T = get_train(c)) {
-        if (T->side) { (void)hipStreamSynchronize(T->side); (void)hipStreamDestroy(T->side); }
-        for (int p = 0; p < TrainPlan::MAXSETS; ++p) for (void* q : {(void*)T->G[p], (void*)T->ACT[p], (void*)T->ACTS[p]}) if (q) (void)hipFree(q);
-        for (int p = 0; p < 2; ++p) {
-            if (T->ev_ready[p]) (void)hipEventDestroy(T->ev_ready[p]);
-            if (T->ev_done[p]) (void)hipEventDestroy(T->ev_done[p]);
-        }
-        if (T->fwd_exec) (void)hipGraphExecDestroy(T->fwd_exec);
-        if (T->bwd_exec) (void)hipGraphExecDestroy(T->bwd_exec);
-        if (T->cap) (void)hipStreamDestroy(T->cap);
-        if (T->h_seed) (void)hipHostFree(T->h_seed);
-        for (void* p : {(void*)T->x_in, (void*)T->out_buf, (void*)T->gout_buf, (void*)T->grads_int, (void*)T->d_seed}) if (p) (void)hipFree(p);
-        for (void* p : {(void*)T->d_jobs, (void*)T->d_wb, (void*)T->d_int, (void*)T->gws, (void*)T->GA, (void*)T->GS, (void*)T->zero_bias, (void*)T->gdense, (void*)T->gta, (void*)T->gh1, (void*)T->four, (void*)T->sig_copy, (void*)T->lab_copy,
-                        (void*)T->d_gemm_jobs, (void*)T->d_col_jobs}) if (p) (void)hipFree(p);
-        if (TiledTrain* tt = T->tiled) {
-            for (void* p : {(void*)tt->gws, (void*)tt->gfin, (void*)tt->act, (void*)tt->dact, (void*)tt->wslab, (void*)tt->cs, (void*)tt->gred, (void*)tt->gslab}) if (p) (void)hipFree(p);
-            delete tt;
-        }
-        train_registry().erase(c);
-        delete T;
-    }
-    for (auto& q : c->progs) for (void* p : {(void*)q.d_fprog, (void*)q.d_ftabs, (void*)q.d_spill, (void*)q.d_xbuf, (void*)q.d_coop_err}) if (p) hipFree(p);
-    void* ptrs[] = {c->d_fprog, c->d_ftabs, c->d_spill, c->d_jobs, c->d_w, c->d_int, c->ws, c->d_h1, c->d_temb, c->d_dense, c->d_s2, c->d_score, c->d_z, c->d_norms, c->d_ts, c->d_tvec, c->d_state, c->d_tt, c->d_th1, c->d_dense_all, c->t_ws, c->t_xin, c->t_out, c->d_w16, c->t_zero};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (auto& ev : c->ev_pool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     delete c;
     return 0;
 }
@@ -2386,12 +2376,12 @@ int rdmi_score(rdmi_ctx* c, const float* x, const float* t, const float* labels,
 static int cf_score_impl(rdmi_ctx* c, const float* x, const float* t, int t_mod, const float* labels, const float* weight,
                          float* out, int B, float smin, float ratio, hipStream_t s) {
     const int E = c->H * c->W * c->arch.channels;
-    FwdIn f{x, B, t, t_mod, 0.f, 1, smin, ratio, labels, B, c->d_s2, 2 * B};
+    FwdIn f{x, B, t, t_mod, 0.f, 1, smin, ratio, labels, B, c->d_s2.get(), 2 * B};
     if (int e = run_forward(c, f, s)) return e;
     {
         ProfScope ps(c, s, "cfg_combine", 0);
         hipLaunchKernelGGL(cfg_combine_kernel, dim3((unsigned)ceil_div(B * E, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s,
-                           (const float*)c->d_s2, weight, out, B, E);
+                           (const float*)c->d_s2.get(), weight, out, B, E);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -2525,23 +2515,23 @@ int rdmi_pc_sample(rdmi_ctx* c, float* x, const float* labels, const float* weig
     // to the shared row in its prologue.
     const int nupd = o->N - 1, T = c->temb, Np_t = (T + 63) & ~63, Np_d = (c->dense_total + 63) & ~63;
     if (c->tt_cap < nupd) {
-        if (c->d_tt) { HIP_OK(hipFree(c->d_tt)); HIP_OK(hipFree(c->d_th1)); HIP_OK(hipFree(c->d_ts)); c->d_tt = c->d_th1 = c->d_ts = nullptr; c->tt_cap = 0; }
-        HIP_OK(hipMalloc((void**)&c->d_tt, (size_t)pad16(nupd) * T * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_th1, (size_t)pad16(nupd) * T * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->d_ts, (size_t)pad16(nupd) * sizeof(float)));
+        c->d_tt.reset(); c->d_th1.reset(); c->d_ts.reset(); c->tt_cap = 0;
+        HIP_OK(hip_alloc(c->d_tt, (size_t)pad16(nupd) * T));
+        HIP_OK(hip_alloc(c->d_th1, (size_t)pad16(nupd) * T));
+        HIP_OK(hip_alloc(c->d_ts, (size_t)pad16(nupd)));
         c->tt_cap = nupd;
     }
     const rdmi_arch& a = c->arch;
     {
         // the time grid is formed on the device by the same double-precision expression as the host copy above (no host
         // buffer has to outlive this call: every rdmi entry point is asynchronous on `stream`)
-        hipLaunchKernelGGL(linspace_kernel, dim3((unsigned)ceil_div(nupd, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, c->d_ts, nupd, o->N, 1.0f, o->eps);
+        hipLaunchKernelGGL(linspace_kernel, dim3((unsigned)ceil_div(nupd, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, c->d_ts.get(), nupd, o->N, 1.0f, o->eps);
         LinArgs l{};
-        l.M = nupd; l.fourW = P(c, "time_embed.W"); l.nfour = a.nf; l.X = c->d_ts; l.x_mod = nupd; l.t_is_time = 1; l.smin = smin; l.ratio = ratio;
-        l.pre = 2; l.K = pad16(2 * a.nf); l.W = c->d_w + c->w_t0; l.Npad = Np_t; l.N = T; l.bias = P(c, "time_mlp.0.bias"); l.Y = c->d_th1; l.ldy = T;
+        l.M = nupd; l.fourW = P(c, "time_embed.W"); l.nfour = a.nf; l.X = c->d_ts.get(); l.x_mod = nupd; l.t_is_time = 1; l.smin = smin; l.ratio = ratio;
+        l.pre = 2; l.K = pad16(2 * a.nf); l.W = c->d_w.get() + c->w_t0; l.Npad = Np_t; l.N = T; l.bias = P(c, "time_mlp.0.bias"); l.Y = c->d_th1.get(); l.ldy = T;
         LinArgs l2{};
-        l2.M = nupd; l2.X = c->d_th1; l2.ldx = T; l2.pre = 1; l2.K = T; l2.W = c->d_w + c->w_t2; l2.Npad = Np_t; l2.N = T;
-        l2.bias = P(c, "time_mlp.2.bias"); l2.Y = c->d_tt; l2.ldy = T;
+        l2.M = nupd; l2.X = c->d_th1.get(); l2.ldx = T; l2.pre = 1; l2.K = T; l2.W = c->d_w.get() + c->w_t2; l2.Npad = Np_t; l2.N = T;
+        l2.bias = P(c, "time_mlp.2.bias"); l2.Y = c->d_tt.get(); l2.ldy = T;
         if (a.conditional) l2.bl = P(c, "label_emb.bias");
         ProfScope ps(c, s, "linear_mfma(time path, all updates)", 2.0 * nupd * T * (2 * a.nf + T));
         hipLaunchKernelGGL(linear_mfma_kernel<1>, dim3((unsigned)ceil_div(nupd, 16), (unsigned)(Np_t / 64)), dim3(RDMI_THREADS), 0, s, l);
@@ -2555,17 +2545,17 @@ int rdmi_pc_sample(rdmi_ctx* c, float* x, const float* labels, const float* weig
     const size_t dense_row_floats = (size_t)NBm * c->dense_total;
     const int U = (int)std::max<size_t>(1, std::min<size_t>((size_t)nupd, ((size_t)256 << 20) / (dense_row_floats * sizeof(float))));
     if (c->dense_all_cap < (size_t)U * dense_row_floats) {
-        if (c->d_dense_all) { HIP_OK(hipFree(c->d_dense_all)); c->d_dense_all = nullptr; c->dense_all_cap = 0; }
-        HIP_OK(hipMalloc((void**)&c->d_dense_all, (size_t)U * dense_row_floats * sizeof(float)));
+        c->dense_all_cap = 0;
+        HIP_OK(hip_alloc(c->d_dense_all, (size_t)U * dense_row_floats));
         c->dense_all_cap = (size_t)U * dense_row_floats;
     }
     auto dense_chunk = [&](int i0) -> int {
         const int u = std::min(U, nupd - i0);
         LinArgs l3{};
-        l3.M = u * NBm; l3.X = c->d_tt + (size_t)i0 * T; l3.ldx = T; l3.pre = 3; l3.K = T; l3.row_div = NBm;
+        l3.M = u * NBm; l3.X = c->d_tt.get() + (size_t)i0 * T; l3.ldx = T; l3.pre = 3; l3.K = T; l3.row_div = NBm;
         if (a.conditional && labels) { l3.labels = labels; l3.Wl = P(c, "label_emb.weight"); l3.ncls = a.num_classes; l3.label_rows = B; }
-        l3.W = c->d_w + c->w_dense; l3.Npad = Np_d; l3.N = c->dense_total;
-        l3.bias = c->d_w + c->b_dense; l3.Y = c->d_dense_all; l3.ldy = c->dense_total;
+        l3.W = c->d_w.get() + c->w_dense; l3.Npad = Np_d; l3.N = c->dense_total;
+        l3.bias = c->d_w.get() + c->b_dense; l3.Y = c->d_dense_all.get(); l3.ldy = c->dense_total;
         ProfScope ps(c, s, "linear_mfma(Dense_0 x all, chunk of updates)", 2.0 * l3.M * T * c->dense_total);
         hipLaunchKernelGGL((linear_mfma_kernel<1, 16>), dim3((unsigned)ceil_div(l3.M, 16), (unsigned)(Np_d / 64)), dim3(RDMI_THREADS), 0, s, l3);
         HIP_OK(hipGetLastError());
@@ -2573,9 +2563,9 @@ int rdmi_pc_sample(rdmi_ctx* c, float* x, const float* labels, const float* weig
     };
     // one score evaluation at update i's shared time: the raw network output lands in d_s2 ([2B] with CFG, [B] without)
     auto net_eval = [&](int i, float t) -> int {
-        FwdIn f{x, o->use_cfg ? B : 0, nullptr, 0, t, 1, smin, ratio, labels, B, c->d_s2, NBm};
-        f.tt_row = c->d_tt + (size_t)i * T;
-        f.dense_rows = c->d_dense_all + (size_t)(i % U) * dense_row_floats;
+        FwdIn f{x, o->use_cfg ? B : 0, nullptr, 0, t, 1, smin, ratio, labels, B, c->d_s2.get(), NBm};
+        f.tt_row = c->d_tt.get() + (size_t)i * T;
+        f.dense_rows = c->d_dense_all.get() + (size_t)(i % U) * dense_row_floats;
         return run_forward(c, f, s);
     };
     uint32_t draw = 0;
@@ -2586,18 +2576,18 @@ int rdmi_pc_sample(rdmi_ctx* c, float* x, const float* labels, const float* weig
             for (int k = 0; k < o->n_steps_each; ++k, ++draw) {
                 if (int e = net_eval(i, t)) return e;
                 ProfScope ps(c, s, "langevin_update", 0);
-                hipLaunchKernelGGL(langevin_prep_kernel, dim3((unsigned)B), dim3(64), 0, s, (const float*)c->d_s2, weight,
-                                   noise ? noise + (size_t)draw * BE : (const float*)nullptr, c->d_score, c->d_z, c->d_norms, B, E,
+                hipLaunchKernelGGL(langevin_prep_kernel, dim3((unsigned)B), dim3(64), 0, s, (const float*)c->d_s2.get(), weight,
+                                   noise ? noise + (size_t)draw * BE : (const float*)nullptr, c->d_score.get(), c->d_z.get(), c->d_norms.get(), B, E,
                                    o->use_cfg, (uint64_t)o->seed, eoff, draw);
                 hipLaunchKernelGGL(langevin_update_kernel, dim3(gBE), dim3(RDMI_THREADS), 64, s, (const float*)x,
-                                   (const float*)c->d_score, (const float*)c->d_z, (const float*)c->d_norms, (const StepState*)nullptr, x,
+                                   (const float*)c->d_score.get(), (const float*)c->d_z.get(), (const float*)c->d_norms.get(), (const StepState*)nullptr, x,
                                    (float*)nullptr, B, E, o->snr, 0);
             }
         }
         if (int e = net_eval(i, t)) return e;
         {
             ProfScope ps(c, s, "em_fused", 0);
-            hipLaunchKernelGGL(em_fused_kernel, dim3(gBE), dim3(RDMI_THREADS), 0, s, (const float*)x, (const float*)c->d_s2, weight,
+            hipLaunchKernelGGL(em_fused_kernel, dim3(gBE), dim3(RDMI_THREADS), 0, s, (const float*)x, (const float*)c->d_s2.get(), weight,
                                noise ? noise + (size_t)draw * BE : (const float*)nullptr, x, trace ? trace + (size_t)i * BE : (float*)nullptr,
                                teacher ? teacher + (size_t)i * BE : (const float*)nullptr, B, E, o->N, t, smin, ratio, gc, o->use_cfg,
                                (uint64_t)o->seed, eoff, draw);
@@ -2632,22 +2622,21 @@ int rdmi_ode_sample(rdmi_ctx* c, float* x, const float* labels, const float* wei
     static const double Bc[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
     static const double Ec[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
     const double SAFETY = 0.9, MIN_FACTOR = 0.2, MAX_FACTOR = 10, err_exp = -1.0 / 5;
-    double *d_y = nullptr, *d_ynew = nullptr, *d_K = nullptr, *d_f1 = nullptr, *d_red = nullptr;
-    float* d_x32 = nullptr;
-    auto cleanup = [&]() { for (void* p : {(void*)d_y, (void*)d_ynew, (void*)d_K, (void*)d_f1, (void*)d_red, (void*)d_x32}) if (p) (void)hipFree(p); };
-#define ODE_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail("%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    ODE_OK(hipMalloc((void**)&d_y, n * sizeof(double)));
-    ODE_OK(hipMalloc((void**)&d_ynew, n * sizeof(double)));
-    ODE_OK(hipMalloc((void**)&d_K, 7 * n * sizeof(double)));
-    ODE_OK(hipMalloc((void**)&d_f1, n * sizeof(double)));
-    ODE_OK(hipMalloc((void**)&d_red, 4 * sizeof(double)));
-    ODE_OK(hipMalloc((void**)&d_x32, n * sizeof(float)));
+    dev_ptr<double> y, ynew, Kd, f1, red;       // y / ynew swap on every accepted step
+    dev_ptr<float> x32;
+    HIP_OK(hip_alloc(y, (size_t)n));
+    HIP_OK(hip_alloc(ynew, (size_t)n));
+    HIP_OK(hip_alloc(Kd, 7 * (size_t)n));
+    HIP_OK(hip_alloc(f1, (size_t)n));
+    HIP_OK(hip_alloc(red, 4));
+    HIP_OK(hip_alloc(x32, (size_t)n));
+    double* const d_K = Kd.get(); double* const d_f1 = f1.get(); double* const d_red = red.get(); float* const d_x32 = x32.get();
     int nfev = 0;
     // fun(t, x32) -> Kout (float64 copy of the float32 drift * bump)
     auto fun = [&](double t, double* Kout) -> int {
-        FwdIn f{d_x32, o->use_cfg ? B : 0, nullptr, 0, (float)t, 1, smin, ratio, labels, B, c->d_s2, NBm};     // vec_t = ones(B) * t  (float32)
+        FwdIn f{d_x32, o->use_cfg ? B : 0, nullptr, 0, (float)t, 1, smin, ratio, labels, B, c->d_s2.get(), NBm};     // vec_t = ones(B) * t  (float32)
         if (int e = run_forward(c, f, s)) return e;
-        hipLaunchKernelGGL(ode_rhs_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const float*)c->d_s2, weight, (const float*)d_x32, Kout, B, E, (float)t, smin, ratio, gc,
+        hipLaunchKernelGGL(ode_rhs_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const float*)c->d_s2.get(), weight, (const float*)d_x32, Kout, B, E, (float)t, smin, ratio, gc,
                            o->use_cfg, o->moll);
         ++nfev;
         return 0;
@@ -2663,20 +2652,20 @@ int rdmi_ode_sample(rdmi_ctx* c, float* x, const float* labels, const float* wei
     const double t0 = o->T, t_bound = o->eps, direction = t_bound >= t0 ? 1.0 : -1.0;
     double t = t0;
     int rc = 0;
-    hipLaunchKernelGGL(ode_f2d_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const float*)x, d_y, n);
-    hipLaunchKernelGGL(ode_stage_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)d_y, (const double*)d_K, n, 0, 0., 0., 0., 0., 0., 0., 0., (double*)nullptr, d_x32);
-    if ((rc = fun(t, d_K))) { cleanup(); return rc; }                // self.f = fun(t0, y0)
+    hipLaunchKernelGGL(ode_f2d_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const float*)x, y.get(), n);
+    hipLaunchKernelGGL(ode_stage_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)y.get(), (const double*)d_K, n, 0, 0., 0., 0., 0., 0., 0., 0., (double*)nullptr, d_x32);
+    if ((rc = fun(t, d_K))) return rc;                // self.f = fun(t0, y0)
     double h_abs;
     if (o->first_step > 0) h_abs = o->first_step;
     else {   // select_initial_step (scipy/integrate/_ivp/common.py), order = 4
         const double interval = std::fabs(t_bound - t0);
         double d0 = 0, d1 = 0, d2 = 0;
-        if ((rc = norm_of(0, d_y, nullptr, d_y, 0, &d0)) || (rc = norm_of(0, d_K, nullptr, d_y, 0, &d1))) { cleanup(); return rc; }
+        if ((rc = norm_of(0, y.get(), nullptr, y.get(), 0, &d0)) || (rc = norm_of(0, d_K, nullptr, y.get(), 0, &d1))) return rc;
         double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
         h0 = std::min(h0, interval);
-        hipLaunchKernelGGL(ode_axpy_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)d_y, (const double*)d_K, h0 * direction, n, d_x32);
-        if ((rc = fun(t0 + h0 * direction, d_f1))) { cleanup(); return rc; }
-        if ((rc = norm_of(1, d_f1, d_K, d_y, 0, &d2))) { cleanup(); return rc; }
+        hipLaunchKernelGGL(ode_axpy_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)y.get(), (const double*)d_K, h0 * direction, n, d_x32);
+        if ((rc = fun(t0 + h0 * direction, d_f1))) return rc;
+        if ((rc = norm_of(1, d_f1, d_K, y.get(), 0, &d2))) return rc;
         d2 /= h0;
         const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 1.0 / 5);
         h_abs = std::min(std::min(100 * h0, h1), interval);
@@ -2689,22 +2678,22 @@ int rdmi_ode_sample(rdmi_ctx* c, float* x, const float* labels, const float* wei
         bool accepted = false, rejected = false;
         double t_new = t, h = 0;
         while (!accepted) {
-            if (h_abs < min_step) { cleanup(); return fail("ode: required step size is less than spacing between numbers (scipy: TOO_SMALL_STEP) at t=%g", t); }
+            if (h_abs < min_step) return fail("ode: required step size is less than spacing between numbers (scipy: TOO_SMALL_STEP) at t=%g", t);
             h = h_abs * direction;
             t_new = t + h;
             if (direction * (t_new - t_bound) > 0) t_new = t_bound;
             h = t_new - t;
             h_abs = std::fabs(h);
             for (int st = 1; st < 6; ++st) {                         // rk_step: K[s] = fun(t + c_s h, y + h * K[:s].T a_s[:s])
-                hipLaunchKernelGGL(ode_stage_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)d_y, (const double*)d_K, n, st, A[st][0], A[st][1], A[st][2], A[st][3],
+                hipLaunchKernelGGL(ode_stage_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)y.get(), (const double*)d_K, n, st, A[st][0], A[st][1], A[st][2], A[st][3],
                                    A[st][4], 0., h, (double*)nullptr, d_x32);
-                if ((rc = fun(t + Cc[st] * h, d_K + (size_t)st * n))) { cleanup(); return rc; }
+                if ((rc = fun(t + Cc[st] * h, d_K + (size_t)st * n))) return rc;
             }
-            hipLaunchKernelGGL(ode_stage_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)d_y, (const double*)d_K, n, 6, Bc[0], Bc[1], Bc[2], Bc[3], Bc[4], Bc[5], h,
-                               d_ynew, d_x32);                       // y_new = y + h * K[:-1].T B
-            if ((rc = fun(t + h, d_K + (size_t)6 * n))) { cleanup(); return rc; }      // f_new -> K[-1]
+            hipLaunchKernelGGL(ode_stage_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)y.get(), (const double*)d_K, n, 6, Bc[0], Bc[1], Bc[2], Bc[3], Bc[4], Bc[5], h,
+                               ynew.get(), d_x32);                       // y_new = y + h * K[:-1].T B
+            if ((rc = fun(t + h, d_K + (size_t)6 * n))) return rc;      // f_new -> K[-1]
             double err = 0;
-            if ((rc = norm_of(2, nullptr, d_ynew, d_y, h, &err))) { cleanup(); return rc; }
+            if ((rc = norm_of(2, nullptr, ynew.get(), y.get(), h, &err))) return rc;
             if (err < 1) {
                 double factor = err == 0 ? MAX_FACTOR : std::min(MAX_FACTOR, SAFETY * std::pow(err, err_exp));
                 if (rejected) factor = std::min(1.0, factor);
@@ -2716,18 +2705,16 @@ int rdmi_ode_sample(rdmi_ctx* c, float* x, const float* labels, const float* wei
             }
         }
         // accept: y <- y_new, f <- f_new (K[0] <- K[6])
-        std::swap(d_y, d_ynew);
-        ODE_OK(hipMemcpyAsync(d_K, d_K + (size_t)6 * n, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        std::swap(y, ynew);
+        HIP_OK(hipMemcpyAsync(d_K, d_K + (size_t)6 * n, n * sizeof(double), hipMemcpyDeviceToDevice, s));
         t = t_new;
         ++steps;
     }
-    hipLaunchKernelGGL(ode_d2f_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)d_y, x, n);
-    ODE_OK(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(ode_d2f_kernel, dim3(gn), dim3(RDMI_THREADS), 0, s, (const double*)y.get(), x, n);
+    HIP_OK(hipStreamSynchronize(s));
     if (nfev_out) *nfev_out = nfev;
     if (t_final) *t_final = t;
     if (o->h_next_out) *o->h_next_out = h_abs;
-    cleanup();
-#undef ODE_OK
     if (c->profiling) prof_collect(c);
     return 0;
 }
@@ -2736,7 +2723,7 @@ int rdmi_ode_sample(rdmi_ctx* c, float* x, const float* labels, const float* wei
 struct rdmi_opt {
     std::vector<OptSlot> h_slots;           // host mirror of the slot table (rdmi_opt_update_slots uploads from here)
     int nslots = 0, nchunks = 0;
-    OptSlot* d_slots = nullptr; OptChunk* d_chunks = nullptr; int* d_first = nullptr; float* d_partial = nullptr; float* d_norm = nullptr;
+    dev_ptr<OptSlot> d_slots; dev_ptr<OptChunk> d_chunks; dev_ptr<int> d_first; dev_ptr<float> d_partial, d_norm;
 };
 
 int rdmi_opt_create(const rdmi_opt_slot* slots, int n, rdmi_opt** out) {
@@ -2751,19 +2738,18 @@ int rdmi_opt_create(const rdmi_opt_slot* slots, int n, rdmi_opt** out) {
         for (unsigned long long o = 0; o < slots[t].numel; o += OPT_CHUNK) chunks.push_back({t, (unsigned)o});
     }
     first[(size_t)n] = (int)chunks.size();
-    rdmi_opt* q = new rdmi_opt();
+    auto q = std::make_unique<rdmi_opt>();
     q->nslots = n; q->nchunks = (int)chunks.size();
-    auto bail = [&](const char* what) { rdmi_opt_destroy(q); return fail("rdmi_opt_create: %s failed", what); };
-    if (hipMalloc((void**)&q->d_slots, (size_t)n * sizeof(OptSlot)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void**)&q->d_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(OptChunk)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void**)&q->d_first, ((size_t)n + 1) * sizeof(int)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void**)&q->d_partial, std::max<size_t>(chunks.size(), 1) * sizeof(float)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void**)&q->d_norm, 2 * sizeof(float)) != hipSuccess) return bail("hipMalloc");
-    if (hipMemcpy(q->d_slots, slots, (size_t)n * sizeof(OptSlot), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
-    if (hipMemcpy(q->d_chunks, chunks.data(), chunks.size() * sizeof(OptChunk), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
-    if (hipMemcpy(q->d_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
+    HIP_OK(hip_alloc(q->d_slots, (size_t)n));
+    HIP_OK(hip_alloc(q->d_chunks, std::max<size_t>(chunks.size(), 1)));
+    HIP_OK(hip_alloc(q->d_first, (size_t)n + 1));
+    HIP_OK(hip_alloc(q->d_partial, std::max<size_t>(chunks.size(), 1)));
+    HIP_OK(hip_alloc(q->d_norm, 2));
+    HIP_OK(hipMemcpy(q->d_slots.get(), slots, (size_t)n * sizeof(OptSlot), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(q->d_chunks.get(), chunks.data(), chunks.size() * sizeof(OptChunk), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(q->d_first.get(), first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
     q->h_slots.assign(reinterpret_cast<const OptSlot*>(slots), reinterpret_cast<const OptSlot*>(slots) + n);
-    *out = q;
+    *out = q.release();
     return 0;
 }
 
@@ -2779,13 +2765,11 @@ int rdmi_opt_update_slots(rdmi_opt* q, const rdmi_opt_slot* slots, int n, void* 
         if ((q->h_slots[(size_t)t].ema == nullptr) != (ns[t].ema == nullptr)) return fail("rdmi_opt_update_slots: slot %d gained or lost its EMA shadow", t);
     }
     q->h_slots.assign(ns, ns + n);
-    HIP_OK(hipMemcpyAsync(q->d_slots, q->h_slots.data(), (size_t)n * sizeof(OptSlot), hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIP_OK(hipMemcpyAsync(q->d_slots.get(), q->h_slots.data(), (size_t)n * sizeof(OptSlot), hipMemcpyHostToDevice, (hipStream_t)stream));
     return 0;
 }
 
 int rdmi_opt_destroy(rdmi_opt* q) {
-    if (!q) return 0;
-    for (void* p : {(void*)q->d_slots, (void*)q->d_chunks, (void*)q->d_first, (void*)q->d_partial, (void*)q->d_norm}) if (p) (void)hipFree(p);
     delete q;
     return 0;
 }
@@ -2804,13 +2788,13 @@ int rdmi_opt_step(rdmi_opt* q, const rdmi_opt_hyper* hy, float* total_norm_out, 
     h.max_norm = hy->max_norm;
     h.one_minus_ema_decay = (float)(1.0 - hy->ema_decay_d);
     h.write_back_grad = hy->write_back_grad;
-    hipLaunchKernelGGL(opt_sumsq_kernel, dim3((unsigned)q->nchunks), dim3(RDMI_THREADS), 16, s, (const OptSlot*)q->d_slots, (const OptChunk*)q->d_chunks, q->d_partial);
-    hipLaunchKernelGGL(opt_norm_kernel, dim3(1), dim3(RDMI_THREADS), RDMI_THREADS * sizeof(float), s, (const float*)q->d_partial, (const int*)q->d_first, q->nslots,
-                       hy->max_norm, q->d_norm);
-    hipLaunchKernelGGL(opt_adam_ema_kernel, dim3((unsigned)q->nchunks), dim3(RDMI_THREADS), 0, s, (const OptSlot*)q->d_slots, (const OptChunk*)q->d_chunks, h,
-                       (const float*)q->d_norm);
+    hipLaunchKernelGGL(opt_sumsq_kernel, dim3((unsigned)q->nchunks), dim3(RDMI_THREADS), 16, s, (const OptSlot*)q->d_slots.get(), (const OptChunk*)q->d_chunks.get(), q->d_partial.get());
+    hipLaunchKernelGGL(opt_norm_kernel, dim3(1), dim3(RDMI_THREADS), RDMI_THREADS * sizeof(float), s, (const float*)q->d_partial.get(), (const int*)q->d_first.get(), q->nslots,
+                       hy->max_norm, q->d_norm.get());
+    hipLaunchKernelGGL(opt_adam_ema_kernel, dim3((unsigned)q->nchunks), dim3(RDMI_THREADS), 0, s, (const OptSlot*)q->d_slots.get(), (const OptChunk*)q->d_chunks.get(), h,
+                       (const float*)q->d_norm.get());
     HIP_OK(hipGetLastError());
-    if (total_norm_out) HIP_OK(hipMemcpyAsync(total_norm_out, q->d_norm, sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (total_norm_out) HIP_OK(hipMemcpyAsync(total_norm_out, q->d_norm.get(), sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -2835,7 +2819,7 @@ int rdmi_get_tap(rdmi_ctx* c, const char* name, float* dst, size_t dst_numel, in
     if (!c->debug_taps) return fail("taps need RDMI_DEBUG_TAPS=1 at rdmi_create (buffers are reused otherwise)");
     if (nm == "temb") {
         if (C) *C = c->temb; if (H) *H = 1; if (W) *W = 1;
-        HIP_OK(hipMemcpyAsync(dst, c->d_temb, std::min(dst_numel, (size_t)c->max_batch * c->temb) * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(dst, c->d_temb.get(), std::min(dst_numel, (size_t)c->max_batch * c->temb) * sizeof(float), hipMemcpyDeviceToDevice, s));
         return 0;
     }
     for (auto& t : c->tensors) {
@@ -2844,7 +2828,7 @@ int rdmi_get_tap(rdmi_ctx* c, const char* name, float* dst, size_t dst_numel, in
         const size_t per = t.per_sample();
         const int nb = (int)std::min<size_t>(dst_numel / per, (size_t)c->max_batch);
         hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)ceil_div((int)(nb * per), RDMI_THREADS)), dim3(RDMI_THREADS), 0, s,
-                           (const float*)(c->ws + t.off * (size_t)c->max_batch), dst, nb, t.H * t.W, t.C, c->arch.compute_dtype == 1 ? 1 : 0);
+                           (const float*)(c->ws.get() + t.off * (size_t)c->max_batch), dst, nb, t.H * t.W, t.C, c->arch.compute_dtype == 1 ? 1 : 0);
         HIP_OK(hipGetLastError());
         return 0;
     }

@@ -23,9 +23,9 @@ struct TiledConvBwd {
 
 struct TiledTrain {
     std::map<int, TiledConvBwd> conv;                  // by launch index
-    float* gws = nullptr;                              // gradient twin of the tiled workspace (t_ws_per_sample * max_batch floats)
-    float* gfin = nullptr;                             // NHWC gradient of the network output
-    float *act = nullptr, *dact = nullptr, *wslab = nullptr, *cs = nullptr, *gred = nullptr, *gslab = nullptr;
+    dev_ptr<float> gws;                                // gradient twin of the tiled workspace (t_ws_per_sample * max_batch floats)
+    dev_ptr<float> gfin;                               // NHWC gradient of the network output
+    dev_ptr<float> act, dact, wslab, cs, gred, gslab;
     static constexpr int MAX_SPLIT = 16;               // weight-gradient K splits (slab depth)
     int last_B = 0; float drop_p = 0.f;
 };
@@ -34,13 +34,13 @@ bool ends_with(const std::string& s, const char* t) { const size_t n = std::strl
 
 inline float* tl_gptr(rdmi_ctx* c, const TiledTrain& tt, size_t off) {
     if (off == rdmi_ctx::TLaunch::NONE || off == rdmi_ctx::TLaunch::XIN) return nullptr;
-    return tt.gws + off * (size_t)c->max_batch;
+    return tt.gws.get() + off * (size_t)c->max_batch;
 }
 
 int tiled_enable_training(rdmi_ctx* c, TrainPlan& T) {
     if (c->arch.compute_dtype != 0) return fail("training on the tiled plan is built for fp32 only (train_dtype='bf16' on this shape is not built)");
-    TiledTrain* tt = new TiledTrain();
-    T.tiled = tt;
+    T.tiled = std::make_unique<TiledTrain>();
+    TiledTrain* tt = T.tiled.get();
     const size_t NBmax = (size_t)c->max_batch;
     T.poff.resize(c->params.size());
     T.ptotal = 0;
@@ -79,28 +79,28 @@ int tiled_enable_training(rdmi_ctx* c, TrainPlan& T) {
         tt->conv[(int)li] = b;
     }
     const size_t E = (size_t)c->H * c->W * c->arch.channels, Mp = (size_t)pad16(c->max_batch);
-    HIP_OK(hipMalloc((void**)&tt->gws, c->t_ws_per_sample * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->gfin, E * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->act, act_f * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->dact, dact_f * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->wslab, slab_f * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->cs, (size_t)cmax * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->gslab, (size_t)cmax * 2 * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&tt->gred, (size_t)32 * 2 * NBmax * sizeof(float)));
+    HIP_OK(hip_alloc(tt->gws, c->t_ws_per_sample * NBmax));
+    HIP_OK(hip_alloc(tt->gfin, E * NBmax));
+    HIP_OK(hip_alloc(tt->act, act_f * NBmax));
+    HIP_OK(hip_alloc(tt->dact, dact_f * NBmax));
+    HIP_OK(hip_alloc(tt->wslab, slab_f));
+    HIP_OK(hip_alloc(tt->cs, (size_t)cmax * NBmax));
+    HIP_OK(hip_alloc(tt->gslab, (size_t)cmax * 2 * NBmax));
+    HIP_OK(hip_alloc(tt->gred, (size_t)32 * 2 * NBmax));
     // embedding backward (embed_backward) and step inputs
-    HIP_OK(hipMalloc((void**)&T.gdense, Mp * c->dense_total * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.gta, Mp * c->temb * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.gh1, Mp * c->temb * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.four, Mp * 2 * c->arch.nf * sizeof(float)));
+    HIP_OK(hip_alloc(T.gdense, Mp * c->dense_total));
+    HIP_OK(hip_alloc(T.gta, Mp * c->temb));
+    HIP_OK(hip_alloc(T.gh1, Mp * c->temb));
+    HIP_OK(hip_alloc(T.four, Mp * 2 * c->arch.nf));
     T.emb_jobs = std::max(64, 2 * (c->dense_total / 32 + 1) + 8);   // two jobs per res block (>= 32 channels each) + the time / label stages
-    HIP_OK(hipMalloc((void**)&T.d_gemm_jobs, (size_t)T.emb_jobs * sizeof(SgemmArgs)));
-    HIP_OK(hipMalloc((void**)&T.d_col_jobs, (size_t)T.emb_jobs * sizeof(ColsumJob)));
+    HIP_OK(hip_alloc(T.d_gemm_jobs, (size_t)T.emb_jobs));
+    HIP_OK(hip_alloc(T.d_col_jobs, (size_t)T.emb_jobs));
     T.h_gemm_jobs.reserve((size_t)T.emb_jobs); T.h_col_jobs.reserve((size_t)T.emb_jobs);
-    HIP_OK(hipMalloc((void**)&T.sig_copy, Mp * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.lab_copy, Mp * std::max(1, c->arch.num_classes) * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.d_seed, 64));
-    HIP_OK(hipMemset(T.d_seed, 0, 64));
-    HIP_OK(hipHostMalloc((void**)&T.h_seed, 64 * sizeof(unsigned long long), 0));
+    HIP_OK(hip_alloc(T.sig_copy, Mp));
+    HIP_OK(hip_alloc(T.lab_copy, Mp * std::max(1, c->arch.num_classes)));
+    HIP_OK(hip_alloc(T.d_seed, 8));
+    HIP_OK(hipMemset(T.d_seed.get(), 0, 64));
+    HIP_OK(hip_alloc(T.h_seed, 64));
     T.use_graph = false;                               // plain launches on the caller's stream
     T.ready = true;
     return 0;
@@ -110,17 +110,17 @@ int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* 
                         uint64_t seed, hipStream_t s) {
     TiledTrain& tt = *T.tiled;
     if (int e = do_repack(c, s)) return e;
-    HIP_OK(hipMemcpyAsync(T.sig_copy, sigma, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (labels) HIP_OK(hipMemcpyAsync(T.lab_copy, labels, (size_t)B * c->arch.num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(T.sig_copy.get(), sigma, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (labels) HIP_OK(hipMemcpyAsync(T.lab_copy.get(), labels, (size_t)B * c->arch.num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
     T.seed_slot = (T.seed_slot + 1) & 63;
-    T.h_seed[T.seed_slot] = seed;
-    HIP_OK(hipMemcpyAsync(T.d_seed, T.h_seed + T.seed_slot, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    T.h_seed.get()[T.seed_slot] = seed;
+    HIP_OK(hipMemcpyAsync(T.d_seed.get(), T.h_seed.get() + T.seed_slot, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     for (auto& kv : tt.conv)
         if (kv.second.dropout) {
             TConvArgs& a = c->tl[(size_t)kv.first].conv;
-            a.drop_p = dropout_p; a.op_id = (uint32_t)kv.first; a.seed_dev = T.d_seed;
+            a.drop_p = dropout_p; a.op_id = (uint32_t)kv.first; a.seed_dev = T.d_seed.get();
         }
-    FwdIn f{x, 0, T.sig_copy, 0, 0.f, 0, 0.f, 0.f, labels ? T.lab_copy : nullptr, B, out, B};
+    FwdIn f{x, 0, T.sig_copy.get(), 0, 0.f, 0, 0.f, 0.f, labels ? T.lab_copy.get() : nullptr, B, out, B};
     const int e = run_forward(c, f, s);
     for (auto& kv : tt.conv) { TConvArgs& a = c->tl[(size_t)kv.first].conv; a.drop_p = 0.f; a.seed_dev = nullptr; }   // sampling stays p = 0
     if (c->profiling) prof_collect(c);
@@ -135,24 +135,24 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
     const TConvArgs& a = l.conv;
     const int Cin = a.CA + a.CB, HWo = a.Ho * a.Wo, HWv = a.Hv * a.Wv;
     auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
-    float* G = l.out_is_final ? tt.gfin : tl_gptr(c, tt, l.oOut);
+    float* G = l.out_is_final ? tt.gfin.get() : tl_gptr(c, tt, l.oOut);
     {   // G = out_scale / sigma_n * dY (in place); residual gradient; column sums
-        const float* sig = (l.out_is_final && c->arch.scale_by_sigma) ? T.sig_copy : nullptr;
+        const float* sig = (l.out_is_final && c->arch.scale_by_sigma) ? T.sig_copy.get() : nullptr;
         ProfScope ps(c, s, "tb_outgrad_kernel", 0);
         hipLaunchKernelGGL(tb_outgrad_kernel, dim3((unsigned)ceil_div(a.Cout, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, (const float*)G, G,
-                           tl_gptr(c, tt, l.oResid), tt.cs, HWo, a.Cout, a.out_scale, sig);
+                           tl_gptr(c, tt, l.oResid), tt.cs.get(), HWo, a.Cout, a.out_scale, sig);
     }
     {
         ProfScope ps(c, s, "tb_bias_kernel", 0);
-        hipLaunchKernelGGL(tb_bias_kernel, dim3((unsigned)ceil_div(a.Cout, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.cs, NB, a.Cout,
-                           pgrad(b.pb[0]), pgrad(b.pb[1]), pgrad(b.pb[2]), b.co_blk, l.use_dense ? T.gdense : (float*)nullptr, c->dense_total, a.dense_off);
+        hipLaunchKernelGGL(tb_bias_kernel, dim3((unsigned)ceil_div(a.Cout, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.cs.get(), NB, a.Cout,
+                           pgrad(b.pb[0]), pgrad(b.pb[1]), pgrad(b.pb[2]), b.co_blk, l.use_dense ? T.gdense.get() : (float*)nullptr, c->dense_total, a.dense_off);
     }
     const bool gn = b.pg >= 0;
     TbGnArgs g{};
     g.A = a.srcA; g.B = a.srcB; g.CA = a.CA; g.CB = a.CB; g.HW = a.Ha * a.Wa; g.NB = NB;
     g.stats = a.stats; g.G = a.G; g.Cg = a.Cg; g.act = a.act; g.gamma = a.gamma; g.beta = a.beta;
-    g.drop_p = b.dropout ? tt.drop_p : 0.f; g.op_id = (uint32_t)b.li; g.seed_dev = T.d_seed;
-    g.ACT = tt.act; g.dACT = tt.dact; g.red = tt.gred; g.gslab = tt.gslab;
+    g.drop_p = b.dropout ? tt.drop_p : 0.f; g.op_id = (uint32_t)b.li; g.seed_dev = T.d_seed.get();
+    g.ACT = tt.act.get(); g.dACT = tt.dact.get(); g.red = tt.gred.get(); g.gslab = tt.gslab.get();
     g.gA = tl_gptr(c, tt, l.oA); g.gB = tl_gptr(c, tt, l.oB);
     g.up = a.up; g.Hv = a.Hv; g.Wv = a.Wv; g.has_gn = gn ? 1 : 0;
     if (gn) {   // the activated input, recomputed (GroupNorm + SiLU + the step's dropout mask)
@@ -164,19 +164,19 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
         w.M = a.Cout; w.N = Cin; w.K = NB * HWo;
         w.Hv = a.Hv; w.Wv = a.Wv; w.Ho = a.Ho; w.Wo = a.Wo; w.stride = a.stride; w.pad = a.pad_lo; w.ntap = a.ntap; w.Cin = Cin; w.Cout = a.Cout;
         w.G = G;
-        if (gn) { w.X = tt.act; w.X2 = nullptr; w.CA = Cin; w.CB = 0; w.Ha = a.Hv; w.Wa = a.Wv; w.up = 0; }
+        if (gn) { w.X = tt.act.get(); w.X2 = nullptr; w.CA = Cin; w.CB = 0; w.Ha = a.Hv; w.Wa = a.Wv; w.up = 0; }
         else { w.X = a.srcA; w.X2 = a.srcB; w.CA = a.CA; w.CB = a.CB; w.Ha = a.Ha; w.Wa = a.Wa; w.up = a.up; }
         const long tiles = (long)ceil_div(a.Cout, 64) * ceil_div(Cin, 64) * a.ntap;
         int ns = (int)std::max(1L, std::min((long)TiledTrain::MAX_SPLIT, 1024 / tiles));
         ns = std::max(1, std::min(ns, ceil_div(w.K, 256)));
         w.kchunk = ceil_div(ceil_div(w.K, ns), 16) * 16; ns = ceil_div(w.K, w.kchunk); w.nsplit = ns;
-        w.out = tt.wslab;
+        w.out = tt.wslab.get();
         {
             ProfScope ps(c, s, "tb_gemm_kernel<wgrad>", 2.0 * NB * HWo * a.ntap * (double)a.Cout * Cin);
             hipLaunchKernelGGL(tb_gemm_kernel<2>, dim3((unsigned)ceil_div(a.Cout, 64), (unsigned)ceil_div(Cin, 64), (unsigned)(a.ntap * ns)), dim3(RDMI_THREADS), 0, s, w);
         }
         ProfScope ps(c, s, "tb_wgrad_reduce_kernel", 0);
-        hipLaunchKernelGGL(tb_wgrad_reduce_kernel, dim3(tb_blocks((long)a.ntap * a.Cout * Cin)), dim3(RDMI_THREADS), 0, s, (const float*)tt.wslab, ns, a.ntap,
+        hipLaunchKernelGGL(tb_wgrad_reduce_kernel, dim3(tb_blocks((long)a.ntap * a.Cout * Cin)), dim3(RDMI_THREADS), 0, s, (const float*)tt.wslab.get(), ns, a.ntap,
                            a.Cout, Cin, pgrad(b.pw[0]), pgrad(b.pw[1]), pgrad(b.pw[2]), b.co_blk, b.w_co, b.w_ci, b.w_t);
     }
     if (l.in_is_x) return 0;                           // no gradient w.r.t. the network input
@@ -187,7 +187,7 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
         d.G = G;
         for (int i = 0; i < 3; ++i) d.W[i] = b.pw[i] >= 0 ? c->params[(size_t)b.pw[i]].ptr : nullptr;
         d.co_blk = b.co_blk; d.w_co = b.w_co; d.w_ci = b.w_ci; d.w_t = b.w_t;
-        d.out = tt.dact;
+        d.out = tt.dact.get();
         ProfScope ps(c, s, "tb_gemm_kernel<dgrad>", 2.0 * NB * HWo * a.ntap * (double)a.Cout * Cin);
         hipLaunchKernelGGL(tb_gemm_kernel<1>, dim3((unsigned)ceil_div(d.M, 64), (unsigned)ceil_div(Cin, 64), 1), dim3(RDMI_THREADS), 0, s, d);
     }
@@ -197,8 +197,8 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
             hipLaunchKernelGGL(tb_gn_red_kernel, dim3((unsigned)a.G, (unsigned)NB), dim3(RDMI_THREADS), 0, s, g);
         }
         ProfScope ps(c, s, "tb_rowsum_kernel", 0);
-        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab, NB, Cin, 2, 0, pgrad(b.pg));
-        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab, NB, Cin, 2, 1, pgrad(b.pbeta));
+        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 0, pgrad(b.pg));
+        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 1, pgrad(b.pbeta));
     }
     ProfScope ps(c, s, "tb_src_grad_kernel", 0);
     hipLaunchKernelGGL(tb_src_grad_kernel, dim3(tb_blocks((long)NB * a.Ha * a.Wa * Cin)), dim3(RDMI_THREADS), 0, s, g);
@@ -245,9 +245,9 @@ int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grad
     // every parameter gradient below is a store; time_embed.W (not trained) stays zero.  The twin takes sums: zeroed (all of it,
     // t_ws_per_sample * max_batch floats -- the tensors are [tensor][sample] blocks, so the first NB samples are not one range)
     HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(tt.gws, 0, c->t_ws_per_sample * NBmax * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(T.gdense, 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(tb_blocks((long)NB * HW * Cc)), dim3(RDMI_THREADS), 0, s, grad_out, tt.gfin, NB, HW, Cc, 0);
+    HIP_OK(hipMemsetAsync(tt.gws.get(), 0, c->t_ws_per_sample * NBmax * sizeof(float), s));
+    HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(tb_blocks((long)NB * HW * Cc)), dim3(RDMI_THREADS), 0, s, grad_out, tt.gfin.get(), NB, HW, Cc, 0);
     for (int li = (int)c->tl.size() - 1; li >= 0; --li) {
         const rdmi_ctx::TLaunch& l = c->tl[(size_t)li];
         if (l.kind == 0) {

@@ -19,30 +19,31 @@ struct BwdConv {
 struct TiledTrain;                       // training on the tiled plan (csrc/tiled_train.h)
 
 struct TrainPlan {
+    ~TrainPlan();                        // defined after tiled_train.h: TiledTrain is complete there
     bool ready = false;
-    TiledTrain* tiled = nullptr;         // non-null: the context runs the tiled plan, and the members below serve its embedding backward
+    std::unique_ptr<TiledTrain> tiled;   // non-null: the context runs the tiled plan, and the members below serve its embedding backward
     std::vector<BwdConv> convs;          // one per forward conv op (same order as c->ops; attention ops are looked up separately)
     std::vector<PackJob> jobs; std::vector<int> job_param;
-    PackJob* d_jobs = nullptr;
-    float* d_wb = nullptr; size_t wb_floats = 0;       // transposed weight packs
-    int* d_int = nullptr;
-    float* gws = nullptr;                // gradients of the activation tensors (same offsets as ws)
+    dev_ptr<PackJob> d_jobs;
+    dev_ptr<float> d_wb; size_t wb_floats = 0;         // transposed weight packs
+    dev_ptr<int> d_int;
+    dev_ptr<float> gws;                  // gradients of the activation tensors (same offsets as ws)
     // scratch of the conv backward.  G / ACT / ACTS exist 2 * group times: the weight-gradient GEMMs of a group of ops run on the
     // side stream while the main stream already produces the next group's G / ACT into the other half (two event pairs per group).
     static constexpr int MAXSETS = 16;
     int group = 8;                       // scratch sets allocated = 2 * group (RDMI_TRAIN_GROUP); conv ops per event pair at run time: group_for(NB)
     bool group_env = false;
     int group_for(int NB) const { return (group_env || NB > 256) ? group : std::min(group, 4); }   // measured at B = 128 bf16: 8 -> 3.76 ms, 4 -> 3.70, 2 -> 3.75, 1 -> 3.92
-    float *G[MAXSETS] = {}, *ACT[MAXSETS] = {}, *ACTS[MAXSETS] = {};
-    float *GA = nullptr, *GS = nullptr, *zero_bias = nullptr;
+    dev_ptr<float> G[MAXSETS], ACT[MAXSETS], ACTS[MAXSETS];
+    dev_ptr<float> GA, GS, zero_bias;
     hipStream_t side = nullptr; hipEvent_t ev_ready[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     bool two_streams = true;             // RDMI_TRAIN_STREAMS=1 keeps everything on the caller's stream
     bool fuse_colsum = true;             // RDMI_TRAIN_FUSE_COLSUM=0: every conv op launches its own bwd_scale_colsum_kernel (diagnostic)
-    float *gdense = nullptr, *gta = nullptr, *gh1 = nullptr, *four = nullptr, *sig_copy = nullptr, *lab_copy = nullptr;
+    dev_ptr<float> gdense, gta, gh1, four, sig_copy, lab_copy;
     std::vector<size_t> poff;            // flat-gradient offset of every parameter
     size_t ptotal = 0;
     float drop_p = 0.f; uint64_t seed = 0; int last_B = 0; int label_rows = 0;
-    SgemmArgs* d_gemm_jobs = nullptr; ColsumJob* d_col_jobs = nullptr;   // job tables of the embedding backward (emb_jobs entries each)
+    dev_ptr<SgemmArgs> d_gemm_jobs; dev_ptr<ColsumJob> d_col_jobs;       // job tables of the embedding backward (emb_jobs entries each)
     int emb_jobs = 64;                   // (the tiled plan's CIFAR shape has 35 res blocks: two Dense_0 jobs each)
     std::vector<SgemmArgs> h_gemm_jobs; std::vector<ColsumJob> h_col_jobs;
     std::vector<SgemmArgs> m_gemm_jobs; std::vector<ColsumJob> m_col_jobs;   // host mirror of what the device tables hold (uploads only on change)
@@ -55,8 +56,8 @@ struct TrainPlan {
     hipGraphExec_t fwd_exec = nullptr, bwd_exec = nullptr;
     std::vector<unsigned long long> fwd_key, bwd_key;     // what a recorded graph depends on (batch, dropout, pointers)
     int fwd_calls = 0, bwd_calls = 0;                     // the first call of each runs eagerly (one-time attribute / table setup happens there)
-    float *x_in = nullptr, *out_buf = nullptr, *gout_buf = nullptr, *grads_int = nullptr;   // grads_int: the flat parameter gradient the recorded backward writes
-    unsigned long long* d_seed = nullptr; unsigned long long* h_seed = nullptr; int seed_slot = 0;   // device seed word; pinned staging ring of 64
+    dev_ptr<float> x_in, out_buf, gout_buf, grads_int;    // grads_int: the flat parameter gradient the recorded backward writes
+    dev_ptr<unsigned long long> d_seed; pinned_ptr<unsigned long long> h_seed; int seed_slot = 0;   // device seed word; pinned staging ring of 64
     std::vector<PackJob> m_jobs_fwd, m_jobs_bwd;          // host mirrors of the two pack-job tables (uploaded only when a parameter pointer changed)
     long graph_replays = 0, graph_records = 0;
     unsigned long long fprog_hash = 0;                    // parameter-pointer hash the training program's descriptors were last patched for
@@ -70,14 +71,6 @@ void conv_tile_cfg(ConvArgs& a, int& cfg) {
     if (cfg == 0 && a.Cout_pad % 64 != 0) { cfg = 1; a.BN = 32; }
     a.Mpad = pad16(a.S * a.HWo);
 }
-
-}  // namespace
-
-struct rdmi_train { TrainPlan t; };
-
-namespace {
-
-std::map<rdmi_ctx*, TrainPlan*>& train_registry() { static std::map<rdmi_ctx*, TrainPlan*> r; return r; }
 
 int tiled_enable_training(rdmi_ctx* c, TrainPlan& T);
 int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* sigma, const float* labels, float* out, int B, float dropout_p,
@@ -124,11 +117,10 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
         size_t top = 0;
         for (auto& t : c->tensors) { t.off = top; top += (t.per_sample() + 63) & ~(size_t)63; }
         c->ws_per_sample = top;
-        if (c->ws) (void)hipFree(c->ws);
-        HIP_OK(hipMalloc((void**)&c->ws, top * NBmax * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.gws, top * NBmax * sizeof(float)));
+        HIP_OK(hip_alloc(c->ws, top * NBmax));
+        HIP_OK(hip_alloc(T.gws, top * NBmax));
         for (auto& op : c->ops) {
-            auto tptr = [&](int t) -> float* { return t >= 0 ? c->ws + c->tensors[(size_t)t].off * NBmax : nullptr; };
+            auto tptr = [&](int t) -> float* { return t >= 0 ? c->ws.get() + c->tensors[(size_t)t].off * NBmax : nullptr; };
             if (op.kind == OP_CONV) {
                 ConvArgs& ca = op.conv;
                 ca.srcA = tptr(op.tA); ca.srcB = tptr(op.tB); ca.scA = tptr(op.tScA); ca.scB = tptr(op.tScB);
@@ -170,20 +162,19 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
             if (op.kind == OP_CONV) { op.conv.a_bf16 = op.a_is_input ? 0 : 1; op.conv.b_bf16 = 1; op.conv.o_bf16 = op.out_is_output ? 0 : 1; }
             else op.attn.io_bf16 = 1;
         }
-        HIP_OK(hipMalloc((void**)&c->d_w16, std::max<size_t>(w16, 64) * sizeof(bf16_t)));
-        HIP_OK(hipMemset(c->d_w16, 0, std::max<size_t>(w16, 64) * sizeof(bf16_t)));
+        HIP_OK(hip_alloc(c->d_w16, std::max<size_t>(w16, 64)));
+        HIP_OK(hipMemset(c->d_w16.get(), 0, std::max<size_t>(w16, 64) * sizeof(bf16_t)));
         size_t k = 0;
         for (auto& op : c->ops) {
             if (op.kind != OP_CONV || !op.conv.bf16) continue;
-            c->jobs[fix[k].first].dst = reinterpret_cast<float*>(c->d_w16 + fix[k].second);
-            op.conv.wpk = reinterpret_cast<const float*>(c->d_w16 + fix[k].second); ++k;
+            c->jobs[fix[k].first].dst = reinterpret_cast<float*>(c->d_w16.get() + fix[k].second);
+            op.conv.wpk = reinterpret_cast<const float*>(c->d_w16.get() + fix[k].second); ++k;
             if (op.conv.Csc) {
-                c->jobs[fix[k].first].dst = reinterpret_cast<float*>(c->d_w16 + fix[k].second);
-                op.conv.wsc = reinterpret_cast<const float*>(c->d_w16 + fix[k].second); ++k;
+                c->jobs[fix[k].first].dst = reinterpret_cast<float*>(c->d_w16.get() + fix[k].second);
+                op.conv.wsc = reinterpret_cast<const float*>(c->d_w16.get() + fix[k].second); ++k;
             }
         }
-        if (c->d_jobs) (void)hipFree(c->d_jobs);
-        HIP_OK(hipMalloc((void**)&c->d_jobs, c->jobs.size() * sizeof(PackJob)));
+        HIP_OK(hip_alloc(c->d_jobs, c->jobs.size()));
         c->packed_valid = false;
     }
     T.poff.resize(c->params.size());
@@ -194,7 +185,7 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
     size_t wb = 0;
     auto alloc_wb = [&](size_t n) { size_t o = wb; wb += (n + 63) & ~(size_t)63; return o; };
     size_t maxG = 1, maxV = 1, maxS = 1;
-    auto gptr = [&](int t) -> float* { return t >= 0 ? T.gws + c->tensors[(size_t)t].off * NBmax : nullptr; };
+    auto gptr = [&](int t) -> float* { return t >= 0 ? T.gws.get() + c->tensors[(size_t)t].off * NBmax : nullptr; };
     (void)gptr;
     T.convs.clear();
     for (size_t oi = 0; oi < c->ops.size(); ++oi) {
@@ -295,20 +286,20 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
         T.convs.push_back(b);
     }
     T.wb_floats = std::max<size_t>(wb, 64);
-    HIP_OK(hipMalloc((void**)&T.d_wb, T.wb_floats * sizeof(float)));
-    HIP_OK(hipMemset(T.d_wb, 0, T.wb_floats * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.d_int, std::max<size_t>(ints.size(), 1) * sizeof(int)));
-    HIP_OK(hipMemcpy(T.d_int, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc((void**)&T.d_jobs, std::max<size_t>(T.jobs.size(), 1) * sizeof(PackJob)));
-    for (auto& j : T.jobs) j.dst = T.d_wb + reinterpret_cast<size_t>(j.dst);
+    HIP_OK(hip_alloc(T.d_wb, T.wb_floats));
+    HIP_OK(hipMemset(T.d_wb.get(), 0, T.wb_floats * sizeof(float)));
+    HIP_OK(hip_alloc(T.d_int, std::max<size_t>(ints.size(), 1)));
+    HIP_OK(hipMemcpy(T.d_int.get(), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OK(hip_alloc(T.d_jobs, std::max<size_t>(T.jobs.size(), 1)));
+    for (auto& j : T.jobs) j.dst = T.d_wb.get() + reinterpret_cast<size_t>(j.dst);
     if (const char* e = getenv("RDMI_TRAIN_STREAMS")) T.two_streams = atoi(e) != 1;
     if (const char* e = getenv("RDMI_TRAIN_FUSE_COLSUM")) T.fuse_colsum = atoi(e) != 0;
     if (const char* e = getenv("RDMI_TRAIN_GROUP")) { T.group = std::max(1, std::min(TrainPlan::MAXSETS / 2, atoi(e))); T.group_env = true; }
     if (!T.two_streams) T.group = 1;
     for (int p = 0; p < 2 * T.group; ++p) {
-        HIP_OK(hipMalloc((void**)&T.G[p], maxG * NBmax * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.ACT[p], maxV * NBmax * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.ACTS[p], maxS * NBmax * sizeof(float)));
+        HIP_OK(hip_alloc(T.G[p], maxG * NBmax));
+        HIP_OK(hip_alloc(T.ACT[p], maxV * NBmax));
+        HIP_OK(hip_alloc(T.ACTS[p], maxS * NBmax));
     }
     for (int p = 0; p < 2; ++p) {
         HIP_OK(hipEventCreateWithFlags(&T.ev_ready[p], hipEventDisableTiming));
@@ -320,29 +311,29 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
         if (pe && atoi(pe) != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) { if (hipStreamCreateWithPriority(&T.side, hipStreamNonBlocking, lo) != hipSuccess) T.side = nullptr; }
         if (!T.side) HIP_OK(hipStreamCreateWithFlags(&T.side, hipStreamNonBlocking));
     }
-    HIP_OK(hipMalloc((void**)&T.GA, maxV * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.GS, maxS * NBmax * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.zero_bias, 1024 * sizeof(float)));
-    HIP_OK(hipMemset(T.zero_bias, 0, 1024 * sizeof(float)));
+    HIP_OK(hip_alloc(T.GA, maxV * NBmax));
+    HIP_OK(hip_alloc(T.GS, maxS * NBmax));
+    HIP_OK(hip_alloc(T.zero_bias, 1024));
+    HIP_OK(hipMemset(T.zero_bias.get(), 0, 1024 * sizeof(float)));
     const size_t Mp = (size_t)pad16(c->max_batch);
-    HIP_OK(hipMalloc((void**)&T.gdense, Mp * c->dense_total * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.gta, Mp * c->temb * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.gh1, Mp * c->temb * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.four, Mp * 2 * c->arch.nf * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.d_gemm_jobs, 64 * sizeof(SgemmArgs)));
-    HIP_OK(hipMalloc((void**)&T.d_col_jobs, 64 * sizeof(ColsumJob)));
+    HIP_OK(hip_alloc(T.gdense, Mp * c->dense_total));
+    HIP_OK(hip_alloc(T.gta, Mp * c->temb));
+    HIP_OK(hip_alloc(T.gh1, Mp * c->temb));
+    HIP_OK(hip_alloc(T.four, Mp * 2 * c->arch.nf));
+    HIP_OK(hip_alloc(T.d_gemm_jobs, 64));
+    HIP_OK(hip_alloc(T.d_col_jobs, 64));
     T.h_gemm_jobs.reserve(64); T.h_col_jobs.reserve(64);
-    HIP_OK(hipMalloc((void**)&T.sig_copy, Mp * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&T.lab_copy, Mp * std::max(1, c->arch.num_classes) * sizeof(float)));
+    HIP_OK(hip_alloc(T.sig_copy, Mp));
+    HIP_OK(hip_alloc(T.lab_copy, Mp * std::max(1, c->arch.num_classes)));
     {
         const size_t E = (size_t)c->H * c->W * c->arch.channels;
-        HIP_OK(hipMalloc((void**)&T.x_in, Mp * E * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.out_buf, Mp * E * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.gout_buf, Mp * E * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.grads_int, std::max<size_t>(T.ptotal, 1) * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&T.d_seed, 64));
-        HIP_OK(hipMemset(T.d_seed, 0, 64));
-        HIP_OK(hipHostMalloc((void**)&T.h_seed, 64 * sizeof(unsigned long long), 0));
+        HIP_OK(hip_alloc(T.x_in, Mp * E));
+        HIP_OK(hip_alloc(T.out_buf, Mp * E));
+        HIP_OK(hip_alloc(T.gout_buf, Mp * E));
+        HIP_OK(hip_alloc(T.grads_int, std::max<size_t>(T.ptotal, 1)));
+        HIP_OK(hip_alloc(T.d_seed, 8));
+        HIP_OK(hipMemset(T.d_seed.get(), 0, 64));
+        HIP_OK(hip_alloc(T.h_seed, 64));
         if (const char* e = getenv("RDMI_TRAIN_GRAPH")) T.use_graph = atoi(e) != 0;
         if (T.use_graph && hipStreamCreateWithFlags(&T.cap, hipStreamNonBlocking) != hipSuccess) { T.cap = nullptr; T.use_graph = false; }
     }
@@ -350,21 +341,15 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
     for (auto& b : T.convs) {
         if (b.has_dgrad) {
             ConvArgs& d = b.dgrad;
-            d.srcA = nullptr; d.tab = T.d_int + b.tab_off; d.wpk = T.d_wb + b.wT_off; d.bias = T.zero_bias; d.out = T.GA;   // srcA = G[parity] at launch
+            d.srcA = nullptr; d.tab = T.d_int.get() + b.tab_off; d.wpk = T.d_wb.get() + b.wT_off; d.bias = T.zero_bias.get(); d.out = T.GA.get();   // srcA = G[parity] at launch
         }
         if (b.has_sc) {
             ConvArgs& d = b.scgrad;
-            d.srcA = nullptr; d.tab = T.d_int + b.sctab_off; d.wpk = T.d_wb + b.wscT_off; d.bias = T.zero_bias; d.out = T.GS;
+            d.srcA = nullptr; d.tab = T.d_int.get() + b.sctab_off; d.wpk = T.d_wb.get() + b.wscT_off; d.bias = T.zero_bias.get(); d.out = T.GS.get();
         }
     }
     T.ready = true;
     return 0;
-}
-
-TrainPlan* get_train(rdmi_ctx* c) {
-    auto& r = train_registry();
-    auto it = r.find(c);
-    return it == r.end() ? nullptr : it->second;
 }
 
 }  // namespace
@@ -373,22 +358,20 @@ extern "C" {
 
 int rdmi_enable_training(rdmi_ctx* c) {
     if (!c) return fail("null context");
-    if (get_train(c)) return 0;
-    TrainPlan* T = new TrainPlan();
+    if (c->train) return 0;
+    auto T = std::make_unique<TrainPlan>();        // installed on the context only once everything below succeeded
     int e = 0;
     try { e = c->tiled ? tiled_enable_training(c, *T) : build_train_plan(c, *T); } catch (const std::exception& ex) { e = fail("training plan: %s", ex.what()); }
-    if (e) { delete T; return e; }
-    train_registry()[c] = T;
-    if (c->tiled) return 0;
+    if (e) return e;
     // The training forward as ONE workgroup-resident launch (the S = 1 fused program + a stash of every layer output + Dropout_0
     // in the GroupNorm_1 epilogues) instead of ~100 layer-plan launches.  RDMI_TRAIN_FUSED=0, or a shape the planner cannot fit,
     // keeps the layer plan's forward.
     const char* tf = getenv("RDMI_TRAIN_FUSED");
-    if (c->fused_ready() && (!tf || atoi(tf) != 0)) {
+    if (!c->tiled && c->fused_ready() && (!tf || atoi(tf) != 0)) {
         if (int e2 = build_one_program(c, 1, false, true)) return e2;
         if (c->progs.back().ok && c->progs.back().train) c->train_prog = (int)c->progs.size() - 1;
-        T->fprog_hash = 0;
     }
+    c->train = std::move(T);
     return 0;
 }
 
@@ -412,11 +395,11 @@ int train_refresh_params(rdmi_ctx* c, TrainPlan& T, hipStream_t s) {
     auto same = [](const std::vector<PackJob>& a, const std::vector<PackJob>& b) { return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(PackJob)) == 0); };
     if (!same(T.m_jobs_fwd, c->jobs)) {
         T.m_jobs_fwd = c->jobs;
-        HIP_OK(hipMemcpyAsync(c->d_jobs, T.m_jobs_fwd.data(), T.m_jobs_fwd.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(c->d_jobs.get(), T.m_jobs_fwd.data(), T.m_jobs_fwd.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
     }
     if (!T.jobs.empty() && !same(T.m_jobs_bwd, T.jobs)) {
         T.m_jobs_bwd = T.jobs;
-        HIP_OK(hipMemcpyAsync(T.d_jobs, T.m_jobs_bwd.data(), T.m_jobs_bwd.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(T.d_jobs.get(), T.m_jobs_bwd.data(), T.m_jobs_bwd.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
     }
     for (auto& op : c->ops) {
         if (op.kind == OP_CONV) {
@@ -433,7 +416,7 @@ int train_refresh_params(rdmi_ctx* c, TrainPlan& T, hipStream_t s) {
         if (q.ok && T.fprog_hash != h) {
             for (auto& f : q.fpatch) {
                 FOp& o = q.fprog[(size_t)f.op];
-                const float* p = f.param.empty() ? c->d_w + f.arena_off : P(c, f.param);
+                const float* p = f.param.empty() ? c->d_w.get() + f.arena_off : P(c, f.param);
                 switch (f.field) {
                     case FusedBuilder::F_GAMMA: o.gamma = p; break;
                     case FusedBuilder::F_BETA: o.beta = p; break;
@@ -444,7 +427,7 @@ int train_refresh_params(rdmi_ctx* c, TrainPlan& T, hipStream_t s) {
                     case FusedBuilder::F_SC1W: o.sc[1].w = p; break;
                 }
             }
-            HIP_OK(hipMemcpyAsync(q.d_fprog, q.fprog.data(), q.fprog.size() * sizeof(FOp), hipMemcpyHostToDevice, s));
+            HIP_OK(hipMemcpyAsync(q.d_fprog.get(), q.fprog.data(), q.fprog.size() * sizeof(FOp), hipMemcpyHostToDevice, s));
             T.fprog_hash = h;
         }
     }
@@ -501,10 +484,10 @@ int embed_backward(rdmi_ctx* c, TrainPlan& T, float* grads_flat, int NB, hipStre
             const int ks = std::max(1, std::min(ceil_div(std::max(mk, 1), 64), 16));
             if (std::memcmp(T.m_gemm_jobs.data() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs)) != 0) {   // same buffers as last step: already resident
                 std::memcpy(T.m_gemm_jobs.data() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs));
-                HIP_OK(hipMemcpyAsync(T.d_gemm_jobs + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs), hipMemcpyHostToDevice, s));
+                HIP_OK(hipMemcpyAsync(T.d_gemm_jobs.get() + g_used, GJ.data() + g_used, nj * sizeof(SgemmArgs), hipMemcpyHostToDevice, s));
             }
             hipLaunchKernelGGL(small_gemm_jobs_kernel, dim3((unsigned)ceil_div(mm, 64), (unsigned)ceil_div(mn, 64), (unsigned)(nj * ks)), dim3(RDMI_THREADS), 0, s,
-                               (const SgemmArgs*)(T.d_gemm_jobs + g_used), ks);
+                               (const SgemmArgs*)(T.d_gemm_jobs.get() + g_used), ks);
             g_used = GJ.size();
             return 0;
         };
@@ -516,10 +499,10 @@ int embed_backward(rdmi_ctx* c, TrainPlan& T, float* grads_flat, int NB, hipStre
             for (size_t i = c_used; i < CJ.size(); ++i) mc = std::max(mc, CJ[i].C);
             if (std::memcmp(T.m_col_jobs.data() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob)) != 0) {
                 std::memcpy(T.m_col_jobs.data() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob));
-                HIP_OK(hipMemcpyAsync(T.d_col_jobs + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob), hipMemcpyHostToDevice, s));
+                HIP_OK(hipMemcpyAsync(T.d_col_jobs.get() + c_used, CJ.data() + c_used, nj * sizeof(ColsumJob), hipMemcpyHostToDevice, s));
             }
             hipLaunchKernelGGL(colsum_jobs_kernel, dim3((unsigned)ceil_div(mc, 64), (unsigned)std::max(1, std::min(64, M / 64)), (unsigned)nj), dim3(RDMI_THREADS), 0, s,
-                               (const ColsumJob*)(T.d_col_jobs + c_used), M, ldx);
+                               (const ColsumJob*)(T.d_col_jobs.get() + c_used), M, ldx);
             c_used = CJ.size();
             return 0;
         };
@@ -528,58 +511,58 @@ int embed_backward(rdmi_ctx* c, TrainPlan& T, float* grads_flat, int NB, hipStre
         for (auto& d : L.down) blocks.push_back({d.name, d.cout});
         blocks.push_back({"mid_block1", L.mid_ch}); blocks.push_back({"mid_block2", L.mid_ch});
         for (auto& u : L.up) blocks.push_back({u.name, u.cout});
-        HIP_OK(hipMemsetAsync(T.gta, 0, (size_t)pad16(c->max_batch) * Tm * sizeof(float), s));
+        HIP_OK(hipMemsetAsync(T.gta.get(), 0, (size_t)pad16(c->max_batch) * Tm * sizeof(float), s));
         int off = 0;
         for (auto& bl : blocks) {
             const int pw = c->pindex.at(bl.first + ".Dense_0.weight"), pb = c->pindex.at(bl.first + ".Dense_0.bias");
             SgemmArgs g{};   // dWd[co][k] = sum_n gdense[n][off+co] * silu(temb[n][k])
-            g.A = T.gdense + off; g.a_m = 1; g.a_k = DT; g.a_act = 0;
-            g.B = c->d_temb; g.b_k = Tm; g.b_n = 1; g.b_act = 1;
+            g.A = T.gdense.get() + off; g.a_m = 1; g.a_k = DT; g.a_act = 0;
+            g.B = c->d_temb.get(); g.b_k = Tm; g.b_n = 1; g.b_act = 1;
             g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1; g.accumulate = 0; g.M = bl.second; g.N = Tm; g.K = NB;
             GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gdense + off, pgrad(pb), bl.second, 0});
+            CJ.push_back(ColsumJob{T.gdense.get() + off, pgrad(pb), bl.second, 0});
             SgemmArgs h{};   // gta[n][k] += sum_co gdense[n][off+co] * Wd[co][k]   (gta zeroed above; the 17 blocks add with atomics)
-            h.A = T.gdense + off; h.a_m = DT; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1;
-            h.C = T.gta; h.c_m = Tm; h.c_n = 1; h.accumulate = 1; h.M = NB; h.N = Tm; h.K = bl.second; h.no_split = 1;
+            h.A = T.gdense.get() + off; h.a_m = DT; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1;
+            h.C = T.gta.get(); h.c_m = Tm; h.c_n = 1; h.accumulate = 1; h.M = NB; h.N = Tm; h.K = bl.second; h.no_split = 1;
             GJ.push_back(h);
             off += bl.second;
         }
         if (int e = flush_gemm()) return e;
         if (int e = flush_col(NB, DT)) return e;
-        hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gta, (const float*)c->d_temb, (long)NB * Tm);
+        hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gta.get(), (const float*)c->d_temb.get(), (long)NB * Tm);
         // gta is now g(temb)
         if (c->arch.conditional) {
             const int pw = c->pindex.at("label_emb.weight"), pb = c->pindex.at("label_emb.bias"), nc = c->arch.num_classes;
             SgemmArgs g{};   // dWl[k][cl] = sum_n gtemb[n][k] * labels[n][cl]
-            g.A = T.gta; g.a_m = 1; g.a_k = Tm; g.B = T.lab_copy; g.b_k = nc; g.b_n = 1; g.C = pgrad(pw); g.c_m = nc; g.c_n = 1;
+            g.A = T.gta.get(); g.a_m = 1; g.a_k = Tm; g.B = T.lab_copy.get(); g.b_k = nc; g.b_n = 1; g.C = pgrad(pw); g.c_m = nc; g.c_n = 1;
             g.M = Tm; g.N = nc; g.K = NB;
             GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gta, pgrad(pb), Tm, 0});
+            CJ.push_back(ColsumJob{T.gta.get(), pgrad(pb), Tm, 0});
         }
         {
             const int pw = c->pindex.at("time_mlp.2.weight"), pb = c->pindex.at("time_mlp.2.bias");
             SgemmArgs g{};   // dW2[k][j] = sum_n gtemb[n][k] * silu(h1[n][j])
-            g.A = T.gta; g.a_m = 1; g.a_k = Tm; g.B = c->d_h1; g.b_k = Tm; g.b_n = 1; g.b_act = 1; g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1;
+            g.A = T.gta.get(); g.a_m = 1; g.a_k = Tm; g.B = c->d_h1.get(); g.b_k = Tm; g.b_n = 1; g.b_act = 1; g.C = pgrad(pw); g.c_m = Tm; g.c_n = 1;
             g.M = Tm; g.N = Tm; g.K = NB;
             GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gta, pgrad(pb), Tm, 0});
+            CJ.push_back(ColsumJob{T.gta.get(), pgrad(pb), Tm, 0});
             SgemmArgs h{};   // gh1[n][j] = sum_k gtemb[n][k] * W2[k][j]
-            h.A = T.gta; h.a_m = Tm; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1; h.C = T.gh1; h.c_m = Tm; h.c_n = 1;
+            h.A = T.gta.get(); h.a_m = Tm; h.a_k = 1; h.B = c->params[(size_t)pw].ptr; h.b_k = Tm; h.b_n = 1; h.C = T.gh1.get(); h.c_m = Tm; h.c_n = 1;
             h.M = NB; h.N = Tm; h.K = Tm; h.no_split = 1;
             GJ.push_back(h);
             if (int e = flush_gemm()) return e;
             if (int e = flush_col(NB, Tm)) return e;
-            hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gh1, (const float*)c->d_h1, (long)NB * Tm);
+            hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)ceil_div(NB * Tm, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, T.gh1.get(), (const float*)c->d_h1.get(), (long)NB * Tm);
         }
         {
             const int pw = c->pindex.at("time_mlp.0.weight"), pb = c->pindex.at("time_mlp.0.bias");
-            hipLaunchKernelGGL(fourier_kernel, dim3((unsigned)ceil_div(NB * 2 * nf, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)T.sig_copy,
-                               c->params[(size_t)c->pindex.at("time_embed.W")].ptr, T.four, NB, nf);
+            hipLaunchKernelGGL(fourier_kernel, dim3((unsigned)ceil_div(NB * 2 * nf, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)T.sig_copy.get(),
+                               c->params[(size_t)c->pindex.at("time_embed.W")].ptr, T.four.get(), NB, nf);
             SgemmArgs g{};   // dW0[j][f] = sum_n gh1[n][j] * four[n][f]
-            g.A = T.gh1; g.a_m = 1; g.a_k = Tm; g.B = T.four; g.b_k = 2 * nf; g.b_n = 1; g.C = pgrad(pw); g.c_m = 2 * nf; g.c_n = 1;
+            g.A = T.gh1.get(); g.a_m = 1; g.a_k = Tm; g.B = T.four.get(); g.b_k = 2 * nf; g.b_n = 1; g.C = pgrad(pw); g.c_m = 2 * nf; g.c_n = 1;
             g.M = Tm; g.N = 2 * nf; g.K = NB;
             GJ.push_back(g);
-            CJ.push_back(ColsumJob{T.gh1, pgrad(pb), Tm, 0});
+            CJ.push_back(ColsumJob{T.gh1.get(), pgrad(pb), Tm, 0});
             if (int e = flush_gemm()) return e;
             if (int e = flush_col(NB, Tm)) return e;
         }
@@ -596,7 +579,7 @@ extern "C" {
 int rdmi_train_forward(rdmi_ctx* c, const float* x, const float* sigma, const float* labels, float* out, int B, float dropout_p,
                        uint64_t seed, void* stream) {
     if (!c || !x || !sigma || !out) return fail("null argument");
-    TrainPlan* T = get_train(c);
+    TrainPlan* T = c->train.get();
     if (!T) return fail("call rdmi_enable_training first");
     if (B < 1 || B > c->max_batch) return fail("batch %d outside [1, %d]", B, c->max_batch);
     hipStream_t s = (hipStream_t)stream;
@@ -605,23 +588,23 @@ int rdmi_train_forward(rdmi_ctx* c, const float* x, const float* sigma, const fl
     T->drop_p = dropout_p; T->seed = seed; T->last_B = B;
     // inputs -> fixed addresses; the seed -> the device word the kernels read
     const size_t E = (size_t)c->H * c->W * c->arch.channels;
-    HIP_OK(hipMemcpyAsync(T->x_in, x, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_OK(hipMemcpyAsync(T->sig_copy, sigma, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (labels) HIP_OK(hipMemcpyAsync(T->lab_copy, labels, (size_t)B * c->arch.num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(T->x_in.get(), x, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(T->sig_copy.get(), sigma, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (labels) HIP_OK(hipMemcpyAsync(T->lab_copy.get(), labels, (size_t)B * c->arch.num_classes * sizeof(float), hipMemcpyDeviceToDevice, s));
     T->seed_slot = (T->seed_slot + 1) & 63;
-    T->h_seed[T->seed_slot] = seed;
-    HIP_OK(hipMemcpyAsync(T->d_seed, T->h_seed + T->seed_slot, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    T->h_seed.get()[T->seed_slot] = seed;
+    HIP_OK(hipMemcpyAsync(T->d_seed.get(), T->h_seed.get() + T->seed_slot, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     auto body = [&](hipStream_t ss) -> int {
         for (size_t oi = 0; oi < c->ops.size(); ++oi) {
             Op& op = c->ops[oi];
-            if (op.kind == OP_CONV) { op.conv.drop_p = op.dropout ? dropout_p : 0.f; op.conv.drop_seed = seed; op.conv.seed_dev = T->d_seed; op.conv.op_id = (uint32_t)oi; }
+            if (op.kind == OP_CONV) { op.conv.drop_p = op.dropout ? dropout_p : 0.f; op.conv.drop_seed = seed; op.conv.seed_dev = T->d_seed.get(); op.conv.op_id = (uint32_t)oi; }
         }
-        hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)c->jobs.size()), dim3(RDMI_THREADS), 0, ss, (const PackJob*)c->d_jobs);
-        FwdIn f{T->x_in, 0, T->sig_copy, 0, 0.f, 0, 0.f, 0.f, labels ? T->lab_copy : nullptr, B, T->out_buf, B};
+        hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)c->jobs.size()), dim3(RDMI_THREADS), 0, ss, (const PackJob*)c->d_jobs.get());
+        FwdIn f{T->x_in.get(), 0, T->sig_copy.get(), 0, 0.f, 0, 0.f, 0.f, labels ? T->lab_copy.get() : nullptr, B, T->out_buf.get(), B};
         const bool keep = c->use_fused;
         c->use_fused = false;                          // (the layer plan, unless the training program exists: run_forward looks at train_prog)
         c->in_train_forward = true;
-        c->train_drop_p = dropout_p; c->train_seed_dev = T->d_seed;
+        c->train_drop_p = dropout_p; c->train_seed_dev = T->d_seed.get();
         const int e = run_forward(c, f, ss);
         c->in_train_forward = false;
         c->use_fused = keep;
@@ -632,7 +615,7 @@ int rdmi_train_forward(rdmi_ctx* c, const float* x, const float* sigma, const fl
     const std::vector<unsigned long long> key{(unsigned long long)B, pb, labels ? 1ull : 0ull, param_ptr_hash(c), c->profiling ? 1ull : 0ull};
     if (c->profiling) { if (int e = body(s)) return e; }         // per-launch events: never from a recorded graph
     else if (int e = run_recorded(*T, T->fwd_exec, T->fwd_key, key, T->fwd_calls, s, body)) return e;
-    HIP_OK(hipMemcpyAsync(out, T->out_buf, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(out, T->out_buf.get(), (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
@@ -640,7 +623,7 @@ int rdmi_train_forward(rdmi_ctx* c, const float* x, const float* sigma, const fl
 // grads_flat in the reference's parameter order (offsets = running sum of numel; time_embed.W stays zero).
 int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t grads_numel, const float* x, void* stream) {
     if (!c || !grad_out || !grads_flat || !x) return fail("null argument");
-    TrainPlan* Tp = get_train(c);
+    TrainPlan* Tp = c->train.get();
     if (!Tp) return fail("call rdmi_enable_training first");
     TrainPlan& T = *Tp;
     if (c->tiled) return tiled_backward(c, T, grad_out, grads_flat, grads_numel, (hipStream_t)stream);
@@ -650,21 +633,21 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
     const size_t NBmax = (size_t)c->max_batch;
     const int sbf = c->arch.compute_dtype == 1;      // bf16 activation workspace and scratch tensors
     if (int e = train_refresh_params(c, T, s0)) return e;
-    x = T.x_in;                                      // the forward's own copy of the input (fixed address)
+    x = T.x_in.get();                                      // the forward's own copy of the input (fixed address)
     {
         const size_t E = (size_t)c->H * c->W * c->arch.channels;
-        HIP_OK(hipMemcpyAsync(T.gout_buf, grad_out, (size_t)NB * E * sizeof(float), hipMemcpyDeviceToDevice, s0));
-        grad_out = T.gout_buf;
+        HIP_OK(hipMemcpyAsync(T.gout_buf.get(), grad_out, (size_t)NB * E * sizeof(float), hipMemcpyDeviceToDevice, s0));
+        grad_out = T.gout_buf.get();
     }
     float* const grads_caller = grads_flat;
-    grads_flat = T.grads_int;                        // fixed address: the recorded launches write here, one copy hands the result to the caller
+    grads_flat = T.grads_int.get();                        // fixed address: the recorded launches write here, one copy hands the result to the caller
     auto body = [&](hipStream_t s) -> int {
     // transposed packs
-    if (!T.jobs.empty()) hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)T.jobs.size()), dim3(RDMI_THREADS), 0, s, (const PackJob*)T.d_jobs);
+    if (!T.jobs.empty()) hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)T.jobs.size()), dim3(RDMI_THREADS), 0, s, (const PackJob*)T.d_jobs.get());
     HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(T.gws, 0, c->ws_per_sample * NBmax * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(T.gdense, 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
-    auto gptr = [&](int t) -> float* { return t >= 0 ? T.gws + c->tensors[(size_t)t].off * NBmax : nullptr; };
+    HIP_OK(hipMemsetAsync(T.gws.get(), 0, c->ws_per_sample * NBmax * sizeof(float), s));
+    HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
+    auto gptr = [&](int t) -> float* { return t >= 0 ? T.gws.get() + c->tensors[(size_t)t].off * NBmax : nullptr; };
     auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
     static bool attr = false;
     if (!attr) {
@@ -696,8 +679,8 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
         const Op& o2 = c->ops[(size_t)oj];
         const BwdConv& b2 = *bmap.at(oj);
         ColsumArgs ca{};
-        ca.gY = o2.out_is_output ? grad_out : gptr(o2.out_tensor); ca.G = T.G[pj]; ca.gR = gptr(o2.tRes); ca.scale = o2.conv.out_scale;
-        ca.gdense = o2.use_dense ? T.gdense : (float*)nullptr; ca.dense_stride = c->dense_total; ca.dense_off = o2.conv.dense_off;
+        ca.gY = o2.out_is_output ? grad_out : gptr(o2.out_tensor); ca.G = T.G[pj].get(); ca.gR = gptr(o2.tRes); ca.scale = o2.conv.out_scale;
+        ca.gdense = o2.use_dense ? T.gdense.get() : (float*)nullptr; ca.dense_stride = c->dense_total; ca.dense_off = o2.conv.dense_off;
         ca.db = pgrad(b2.p_b); ca.db2 = pgrad(b2.p_bsc); ca.HW = o2.conv.HWo; ca.C = o2.spec.Cout; ca.g_bf16 = sbf;
         return ca;
     };
@@ -724,7 +707,7 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
         const float* gY = op.out_is_output ? grad_out : gptr(op.out_tensor);
         const int p = nconv % (2 * grp), half = p / grp;
         ++nconv;
-        float* Gp = T.G[p]; float* ACTp = T.ACT[p]; float* ACTSp = T.ACTS[p];
+        float* Gp = T.G[p].get(); float* ACTp = T.ACT[p].get(); float* ACTSp = T.ACTS[p].get();
         if (T.two_streams && p % grp == 0 && done_rec[half] && !colsum_fused) HIP_OK(hipStreamWaitEvent(s, T.ev_done[half], 0));   // the group before last has left this half
         // G = scale * gY (+ identity residual) and the bias / NIN-bias / Dense_0 gradients (column sums of G): its own launch only where the
         // previous backward kernel was not a GroupNorm backward that could carry it as its tail (first op, ops behind an attention block)
@@ -751,13 +734,13 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
             GnBwdArgs g{};
             g.srcA = op.a_is_input ? x : fa.srcA; g.srcB = fa.srcB; g.mapA = fa.mapA;
             g.CA = fa.CA; g.CB = fa.CB; g.Cv = fa.Cv; g.HWa = fa.HWa; g.HWv = fa.HWv; g.srcA_mod = 0; g.NB = NB;
-            g.GA = T.GA; g.ACT = ACTp; g.a_bf16 = op.a_is_input ? 0 : sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
+            g.GA = T.GA.get(); g.ACT = ACTp; g.a_bf16 = op.a_is_input ? 0 : sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
             g.has_gn = b.has_gn ? 1 : 0; g.G = fa.G; g.eps = fa.eps;
             if (b.has_gn) { g.gamma = fa.gamma; g.beta = fa.beta; g.dgamma = pgrad(b.p_gamma); g.dbeta = pgrad(b.p_beta); }
-            g.drop_p = op.dropout ? T.drop_p : 0.f; g.seed = T.seed; g.seed_dev = T.d_seed; g.op_id = (uint32_t)oi;
+            g.drop_p = op.dropout ? T.drop_p : 0.f; g.seed = T.seed; g.seed_dev = T.d_seed.get(); g.op_id = (uint32_t)oi;
             if (b.has_dgrad) {
                 g.gA = gptr(op.tA); g.gB = gptr(op.tB);
-                if (b.has_invA) { g.inv_start = T.d_int + b.invA_start; g.inv_list = T.d_int + b.invA_list; }
+                if (b.has_invA) { g.inv_start = T.d_int.get() + b.invA_start; g.inv_list = T.d_int.get() + b.invA_list; }
             }
             const size_t lds = gn_bwd_lds_bytes(fa.HWv, fa.Cv);
             if (lds > 160 * 1024) return fail("gn backward of %s: LDS %zu B", sp.name.c_str(), lds);
@@ -771,16 +754,16 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
             GnBwdArgs g{};
             g.srcA = fa.scA; g.srcB = fa.scB; g.mapA = fa.mapSc;
             g.CA = fa.CscA; g.CB = fa.CscB; g.Cv = fa.Csc; g.HWa = fa.HWsa; g.HWv = fa.HWo; g.NB = NB;
-            g.GA = T.GS; g.ACT = ACTSp; g.has_gn = 0; g.a_bf16 = sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
+            g.GA = T.GS.get(); g.ACT = ACTSp; g.has_gn = 0; g.a_bf16 = sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
             g.gA = gptr(op.tScA); g.gB = gptr(op.tScB);
-            if (b.has_invS) { g.inv_start = T.d_int + b.invS_start; g.inv_list = T.d_int + b.invS_list; }
+            if (b.has_invS) { g.inv_start = T.d_int.get() + b.invS_start; g.inv_list = T.d_int.get() + b.invS_list; }
             g.tail = tail;
             hipLaunchKernelGGL(gn_bwd_kernel, dim3((unsigned)NB), dim3(GN_THREADS), gn_bwd_lds_bytes(fa.HWo, fa.Csc), s, g);
         }
         // weight gradients on the side stream (reference OIHW layout): dW[co][ci][t] += sum ACT[in(o,t)][ci] G[o][co];  NIN: dWn += Vs^T G
         {
             WgradArgs w{};
-            w.ACT = ACTp; w.G = Gp; w.dW = pgrad(b.p_w); w.tab = T.d_int + b.wtab_off;
+            w.ACT = ACTp; w.G = Gp; w.dW = pgrad(b.p_w); w.tab = T.d_int.get() + b.wtab_off;
             w.NB = NB; w.HWv = fa.HWv; w.HWo = fa.HWo; w.Cin = Cin; w.Cout = sp.Cout; w.ntap = 9;
             w.lda = fa.Cv;                                   // ACT has Cv (padded) channels per pixel; only ci < Cin are real
             w.s_co = (long)Cin * 9; w.s_ci = 9; w.s_t = 1;
@@ -809,13 +792,13 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
     unsigned pb; std::memcpy(&pb, &T.drop_p, 4);
     const std::vector<unsigned long long> key{(unsigned long long)NB, pb, param_ptr_hash(c)};
     if (int e = run_recorded(T, T.bwd_exec, T.bwd_key, key, T.bwd_calls, s0, body)) return e;
-    HIP_OK(hipMemcpyAsync(grads_caller, T.grads_int, T.ptotal * sizeof(float), hipMemcpyDeviceToDevice, s0));
+    HIP_OK(hipMemcpyAsync(grads_caller, T.grads_int.get(), T.ptotal * sizeof(float), hipMemcpyDeviceToDevice, s0));
     return 0;
 }
 
 // Diagnostic: how often the training step's launch graphs were recorded and replayed (tests: the recorded path is what runs).
 int rdmi_train_graph_stats(rdmi_ctx* c, long* records, long* replays) {
-    TrainPlan* T = c ? get_train(c) : nullptr;
+    TrainPlan* T = c ? c->train.get() : nullptr;
     if (!T || !records || !replays) return fail("no training plan");
     *records = T->graph_records; *replays = T->graph_replays;
     return 0;

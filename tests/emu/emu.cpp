@@ -185,3 +185,29 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
     return hipSuccess;
 }
+
+// ---- memory: calloc'd blocks, counted.  Tests reach the counter and the injected failure through the two functions below (ctypes).
+static std::atomic<long> live_blocks{0};
+static std::atomic<long> fail_countdown{-1};      // allocations left before the one that fails; -1: none fails
+
+static hipError_t emu_alloc(void** p, size_t n) {
+    *p = nullptr;
+    if (fail_countdown.load() >= 0 && fail_countdown.fetch_sub(1) == 0) return hipErrorOutOfMemory;
+    *p = std::calloc(1, n ? n : 1);
+    if (!*p) return hipErrorOutOfMemory;
+    ++live_blocks;
+    return hipSuccess;
+}
+static hipError_t emu_free(void* p) {
+    if (p) { std::free(p); --live_blocks; }
+    return hipSuccess;
+}
+hipError_t hipMalloc(void** p, size_t n) { return emu_alloc(p, n); }
+hipError_t hipFree(void* p) { return emu_free(p); }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { return emu_alloc(p, n); }
+hipError_t hipHostFree(void* p) { return emu_free(p); }
+
+// blocks allocated by hipMalloc / hipHostMalloc and not yet freed
+extern "C" long rdmi_emu_live_blocks() { return live_blocks.load(); }
+// the k-th allocation from now on (0: the next one) returns hipErrorOutOfMemory, once; k < 0 disarms
+extern "C" void rdmi_emu_fail_alloc(long k) { fail_countdown.store(k < 0 ? -1 : k); }

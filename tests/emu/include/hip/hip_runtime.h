@@ -135,10 +135,11 @@ enum hipStreamCaptureMode { hipStreamCaptureModeGlobal, hipStreamCaptureModeThre
 
 inline const char* hipGetErrorString(hipError_t e) { return e == 0 ? "ok" : "emu error"; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
-inline hipError_t hipMalloc(void** p, size_t n) { *p = std::calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = std::calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
+// device and pinned host blocks are counted, and an allocation can be made to fail (emu.cpp: rdmi_emu_live_blocks / rdmi_emu_fail_alloc)
+hipError_t hipMalloc(void** p, size_t n);
+hipError_t hipFree(void* p);
+hipError_t hipHostMalloc(void** p, size_t n, unsigned flags);
+hipError_t hipHostFree(void* p);
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memmove(d, s, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return hipSuccess; }
