@@ -131,6 +131,11 @@ int rdmi_enable_training(rdmi_ctx* ctx);
 int rdmi_train_forward(rdmi_ctx* ctx, const float* x, const float* sigma, const float* labels, float* out, int B,
                        float dropout_p, uint64_t seed, void* stream);
 int rdmi_backward(rdmi_ctx* ctx, const float* grad_out, float* grads_flat, size_t grads_numel, const float* x, void* stream);
+/* As rdmi_backward, plus grad_x [B,C,H,W] = d<grad_out, out>/dx (written, not accumulated; may be NULL).
+ * grads_flat may be NULL (grads_numel ignored): VJP-only mode -- no parameter gradient is computed.  Both NULL is an error.
+ * rdmi_backward is this call with grad_x = NULL.  grad_x is run-to-run identical (one writer per element, no atomics). */
+int rdmi_backward_input(rdmi_ctx* ctx, const float* grad_out, float* grads_flat, size_t grads_numel, float* grad_x, const float* x,
+                        void* stream);
 /* Diagnostic: the train-mode forward and the backward are recorded as launch graphs on their second call and replayed from then on
  * (RDMI_TRAIN_GRAPH=0: plain launches): how many recordings and replays this context has made. */
 int rdmi_train_graph_stats(rdmi_ctx* ctx, long* records, long* replays);
@@ -141,6 +146,12 @@ int rdmi_train_graph_stats(rdmi_ctx* ctx, long* records, long* replays);
 int rdmi_em_update(const float* x, const float* score, const float* z, const float* t, float* x_out,
                    float* x_mean_out, int B, int elems_per_sample, int N, double sigma_min, double sigma_max,
                    void* stream);
+
+/* Probability-flow drift and Hutchinson divergence of RVESDE from a score and its VJP gx = d<eps, score>/dx (the right-hand side of
+ * the likelihood ODE): drift[b,e] = -0.5 g(t_b)^2 score[b,e];  div[b] = -0.5 g(t_b)^2 * sum_e gx[b,e] * eps[b,e], with
+ * g(t) = sigma(t) sqrt(2 ln(sigma_max/sigma_min)) formed in double.  Fixed-order reduction, no atomics.  t, div: device [B]. */
+int rdmi_pf_drift_div(const float* score, const float* gx, const float* eps, const float* t, float* drift, float* div, int B,
+                      int elems_per_sample, double sigma_min, double sigma_max, void* stream);
 
 /* One reflected Langevin corrector step given the score (RD/sampling.py:222-231); the step
  * size uses the means over THIS batch of ||score_b|| and ||z_b||.  scratch: device [2*B+2]. */

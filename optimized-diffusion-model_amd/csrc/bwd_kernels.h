@@ -122,7 +122,8 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_kernel(GnBwdArgs a) {
     __syncthreads();
     const size_t base = (size_t)n * a.HWv * a.Cv;               // element offset of this sample in ACT / GA
     if (!a.has_gn) {
-        for (int i = tid; i < a.HWv * a.Cv; i += GN_THREADS) { const int v = i / a.Cv, c = i - v * a.Cv; stact1(a.ACT, base + i, V[(size_t)v * rs + c], a.s_bf16); }
+        if (a.ACT)
+            for (int i = tid; i < a.HWv * a.Cv; i += GN_THREADS) { const int v = i / a.Cv, c = i - v * a.Cv; stact1(a.ACT, base + i, V[(size_t)v * rs + c], a.s_bf16); }
     } else {
         const int G = a.G, Cg = a.Cv / G, cnt = Cg * a.HWv;
         const int T = min(64, GN_THREADS / G);                    // G in {16, 32} -> T in {64, 32} lanes per group (inside one wave)
@@ -152,7 +153,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_kernel(GnBwdArgs a) {
                     const float y = xh * gm + bt;
                     const float sg = 1.0f / (1.0f + __expf(-y));
                     const float ds = dropout_scale(a.seed_dev ? (uint64_t)*a.seed_dev : a.seed, a.op_id, ((uint64_t)n * a.HWv + v) * a.Cv + c, a.drop_p);
-                    stact1(a.ACT, base + (size_t)v * a.Cv + c, y * sg * ds, a.s_bf16);
+                    if (a.ACT) stact1(a.ACT, base + (size_t)v * a.Cv + c, y * sg * ds, a.s_bf16);
                     const float gy = Gt[(size_t)v * rs + c] * ds * (sg * (1.0f + y * (1.0f - sg)));
                     dg += gy * xh; dbt += gy;
                     V[(size_t)v * rs + c] = xh;
@@ -160,8 +161,8 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_kernel(GnBwdArgs a) {
                 }
             }
             red[tid] = dg; red[GN_THREADS + tid] = dbt;
-            __syncthreads();
-            if (tid < a.Cv) {
+            __syncthreads();                                     // (also orders the V / Gt writes above before the group sums below)
+            if (a.dgamma && tid < a.Cv) {                        // null in VJP-only mode: the channel sums go nowhere
                 float sg2 = 0.f, sb2 = 0.f;
                 for (int j = 0; j < R; ++j) { sg2 += red[j * a.Cv + tid]; sb2 += red[GN_THREADS + j * a.Cv + tid]; }
                 atomicAdd(a.dgamma + tid, sg2);
@@ -814,7 +815,8 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_kernel(AttnBwdArgs a) {
         }
         __syncthreads();
     }
-    // ---- flush the per-workgroup parameter gradients (tile roles as in phases D and H)
+    // ---- flush the per-workgroup parameter gradients (tile roles as in phases D and H); VJP-only mode passes null and drops them
+    if (!a.dW[0]) return;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -836,6 +838,72 @@ __global__ __launch_bounds__(AB_THREADS) void attn_bwd_kernel(AttnBwdArgs a) {
             atomicAdd(outs[q] + tid, sum);
         }
     }
+}
+
+// Data gradient of input_conv (3x3, stride 1, pad 1; C = image channels <= IDG_MAXC, Cout = nf), straight to the caller's NCHW layout:
+//   gx[n][ci][y][x] = sum_{ky, kx, co} G[n][y + 1 - ky][x + 1 - kx][co] * W[co][ci][ky][kx]
+// (a tap whose output pixel lies outside the image contributes nothing: the forward's tap validity).  Through the MFMA data-gradient
+// tiles N = C would be > 80 % padding, so this is a direct kernel: the 16 lanes of a DPP row own one input pixel, read the <= 9
+// neighbouring rows of G (NHWC, fp32 or the bf16 layer plan's bf16) contiguously along co with one 128-bit load per lane and pass, and
+// multiply with the weights staged in LDS as [tap][ci][co] (a row's 16 lanes read consecutive 16 B; the 4 rows of a wave the same
+// addresses: broadcast).  fp32 accumulation, a fixed-order row reduction and one writer per output element: run-to-run identical.
+#define IDG_LANES 16
+#define IDG_MAXC 4
+struct InputDgradArgs { const float* G; const float* W; float* gx; int NB, H, Wd, C, Cout; };
+__host__ __device__ inline size_t input_dgrad_lds_bytes(int C, int Cout) { return (size_t)9 * C * Cout * sizeof(float); }
+template <bool BF16>
+__global__ __launch_bounds__(RDMI_THREADS) void input_dgrad_kernel(InputDgradArgs a) {
+    constexpr int VW = BF16 ? 8 : 4;                             // channels per 128-bit load
+    float* Ws = reinterpret_cast<float*>(rdmi_lds);              // [9][C][Cout]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 9 * a.C * a.Cout; i += RDMI_THREADS) {
+        const int co = i % a.Cout, r = i / a.Cout, ci = r % a.C, t = r / a.C;
+        Ws[i] = a.W[((size_t)co * a.C + ci) * 9 + t];            // parameter layout OIHW
+    }
+    __syncthreads();
+    const int HW = a.H * a.Wd, sub = tid & (IDG_LANES - 1);
+    const long pix = (long)blockIdx.x * (RDMI_THREADS / IDG_LANES) + tid / IDG_LANES;
+    const bool live = pix < (long)a.NB * HW;                     // (no early return: the row reduction below takes every lane)
+    const long pc = live ? pix : 0;
+    const int n = (int)(pc / HW), v = (int)(pc - (long)n * HW), y = v / a.Wd, x = v - y * a.Wd;
+    float acc[IDG_MAXC];
+#pragma unroll
+    for (int ci = 0; ci < IDG_MAXC; ++ci) acc[ci] = 0.f;
+    if (live)
+        for (int t = 0; t < 9; ++t) {
+            const int oy = y + 1 - t / 3, ox = x + 1 - t % 3;
+            if (oy < 0 || oy >= a.H || ox < 0 || ox >= a.Wd) continue;
+            const size_t row = ((size_t)n * HW + (size_t)oy * a.Wd + ox) * a.Cout;
+            for (int c0 = sub * VW; c0 < a.Cout; c0 += IDG_LANES * VW) {
+                float g[VW];
+                if (BF16) {
+                    typedef unsigned int u32x4 __attribute__((vector_size(16)));
+                    const u32x4 u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(a.G) + row + c0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { g[2 * j] = __builtin_bit_cast(float, u[j] << 16); g[2 * j + 1] = __builtin_bit_cast(float, u[j] & 0xffff0000u); }
+                } else {
+                    const f32x4 u = *reinterpret_cast<const f32x4*>(a.G + row + c0);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) g[j] = u[j];
+                }
+#pragma unroll
+                for (int ci = 0; ci < IDG_MAXC; ++ci)
+                    if (ci < a.C) {
+                        const float* w = Ws + (size_t)(t * a.C + ci) * a.Cout + c0;
+#pragma unroll
+                        for (int j = 0; j < VW; j += 4) {
+                            const f32x4 w4 = *reinterpret_cast<const f32x4*>(w + j);
+                            acc[ci] += g[j] * w4[0] + g[j + 1] * w4[1] + g[j + 2] * w4[2] + g[j + 3] * w4[3];
+                        }
+                    }
+            }
+        }
+#pragma unroll
+    for (int ci = 0; ci < IDG_MAXC; ++ci) acc[ci] = row16_sum(acc[ci]);
+    if (live && sub == 0)
+#pragma unroll
+        for (int ci = 0; ci < IDG_MAXC; ++ci)
+            if (ci < a.C) a.gx[((size_t)n * a.C + ci) * HW + v] = acc[ci];
 }
 
 // loss backward: gscore[i] = gper[b] * dper_dscore[i]

@@ -82,3 +82,32 @@ __global__ __launch_bounds__(RDMI_THREADS) void ode_d2f_kernel(const double* __r
     const long i = (long)blockIdx.x * RDMI_THREADS + threadIdx.x;
     if (i < n) x[i] = (float)y[i];
 }
+
+// Right-hand side of the likelihood ODE (probability flow of RVESDE + Hutchinson divergence) from a score and its vector-Jacobian
+// product gx = d<eps, score>/dx, one workgroup per sample:
+//   drift[b, e] = c_b * score[b, e],   div[b] = c_b * sum_e gx[b, e] * eps[b, e],   c_b = -0.5 g(t_b)^2,
+//   g(t) = sigma_min (sigma_max / sigma_min)^t * sqrt(2 ln(sigma_max / sigma_min))     (RD/sde_lib.py:135-140)
+// c_b is formed in double and rounded once; the products and the sum run in double in a fixed order (strided per work-item, then an
+// LDS tree): no atomics, run-to-run identical, and the cancellation of a signed sum of E terms costs no fp32 digits.
+__global__ __launch_bounds__(RDMI_THREADS) void pf_drift_div_kernel(const float* __restrict__ score, const float* __restrict__ gx, const float* __restrict__ eps,
+                                                                     const float* __restrict__ t, float* __restrict__ drift, float* __restrict__ div, int E,
+                                                                     double smin, double ratio, double g2const) {
+    __shared__ double red[RDMI_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const double sigma = smin * pow(ratio, (double)t[b]);
+    const double cd = -0.5 * sigma * sigma * g2const;
+    const float cf = (float)cd;
+    const size_t base = (size_t)b * E;
+    double acc = 0.0;
+    for (int e = tid; e < E; e += RDMI_THREADS) {
+        drift[base + e] = cf * score[base + e];
+        acc += (double)gx[base + e] * (double)eps[base + e];
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int m = RDMI_THREADS / 2; m >= 1; m >>= 1) {
+        if (tid < m) red[tid] += red[tid + m];
+        __syncthreads();
+    }
+    if (tid == 0) div[b] = (float)(cd * red[0]);
+}

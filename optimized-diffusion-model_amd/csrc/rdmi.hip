@@ -2208,7 +2208,7 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
 TrainPlan::~TrainPlan() {
     if (side) (void)hipStreamSynchronize(side);
     if (fwd_exec) (void)hipGraphExecDestroy(fwd_exec);
-    if (bwd_exec) (void)hipGraphExecDestroy(bwd_exec);
+    for (auto& e : bwd_exec) if (e) (void)hipGraphExecDestroy(e);
     for (int p = 0; p < 2; ++p) {
         if (ev_ready[p]) (void)hipEventDestroy(ev_ready[p]);
         if (ev_done[p]) (void)hipEventDestroy(ev_done[p]);
@@ -2268,6 +2268,7 @@ const char* rdmi_path_info(rdmi_ctx* c) {
     for (auto& q : c->progs) if (q.train && !q.ok) s += "; fused training forward unavailable (" + q.why + ")";
     if (c->train_prog >= 0 && c->progs[(size_t)c->train_prog].ok)
         s += "; training forward: fused program (" + std::to_string(c->progs[(size_t)c->train_prog].fprog.size()) + " ops, layer outputs stashed for the backward)";
+    if (c->train) s += "; input-gradient backward calls: " + std::to_string(c->train->input_dgrad_calls);
     return s.c_str();
 }
 
@@ -2469,6 +2470,16 @@ int rdmi_em_update(const float* x, const float* score, const float* z, const flo
                        (hipStream_t)stream, x, score, z, t, (const float*)nullptr, (const StepState*)nullptr, x_out,
                        x_mean_out, (float*)nullptr, B, E, N, (float)sigma_min, (float)(sigma_max / sigma_min),
                        g_const(sigma_min, sigma_max), 0);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int rdmi_pf_drift_div(const float* score, const float* gx, const float* eps, const float* t, float* drift, float* div, int B, int E,
+                      double sigma_min, double sigma_max, void* stream) {
+    if (!score || !gx || !eps || !t || !drift || !div) return fail("null argument");
+    if (B < 1 || E < 1) return fail("pf_drift_div: %d samples of %d elements", B, E);
+    hipLaunchKernelGGL(pf_drift_div_kernel, dim3((unsigned)B), dim3(RDMI_THREADS), 0, (hipStream_t)stream, score, gx, eps, t, drift, div, E, sigma_min,
+                       sigma_max / sigma_min, 2.0 * (std::log(sigma_max) - std::log(sigma_min)));
     HIP_OK(hipGetLastError());
     return 0;
 }

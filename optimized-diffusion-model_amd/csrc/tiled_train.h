@@ -130,10 +130,15 @@ int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* 
 
 inline unsigned tb_blocks(long n) { return (unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS); }
 
-// backward of one conv launch: G (in place) -> bias / Dense_0 -> weight gradient -> data gradient -> GroupNorm / resampling adjoint
-int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ctx::TLaunch& l, const TiledConvBwd& b, float* grads_flat, int NB, hipStream_t s) {
+// backward of one conv launch: G (in place) -> bias / Dense_0 -> weight gradient -> data gradient -> GroupNorm / resampling adjoint.
+// grads_flat == null (VJP-only): the launches that feed only parameter gradients are left out (bias / Dense_0 sums, the activation
+// recompute and the weight-gradient contraction with its slab reduce, the gamma / beta row sums).  grad_x != null: the input conv's
+// data gradient goes straight to the caller's NCHW grad_x (input_dgrad_kernel; no gradient twin of the input exists).
+int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ctx::TLaunch& l, const TiledConvBwd& b, float* grads_flat, float* grad_x, int NB,
+                        hipStream_t s) {
     const TConvArgs& a = l.conv;
     const int Cin = a.CA + a.CB, HWo = a.Ho * a.Wo, HWv = a.Hv * a.Wv;
+    const bool want_p = grads_flat != nullptr;
     auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
     float* G = l.out_is_final ? tt.gfin.get() : tl_gptr(c, tt, l.oOut);
     {   // G = out_scale / sigma_n * dY (in place); residual gradient; column sums
@@ -142,7 +147,7 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
         hipLaunchKernelGGL(tb_outgrad_kernel, dim3((unsigned)ceil_div(a.Cout, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, (const float*)G, G,
                            tl_gptr(c, tt, l.oResid), tt.cs.get(), HWo, a.Cout, a.out_scale, sig);
     }
-    {
+    if (want_p) {
         ProfScope ps(c, s, "tb_bias_kernel", 0);
         hipLaunchKernelGGL(tb_bias_kernel, dim3((unsigned)ceil_div(a.Cout, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.cs.get(), NB, a.Cout,
                            pgrad(b.pb[0]), pgrad(b.pb[1]), pgrad(b.pb[2]), b.co_blk, l.use_dense ? T.gdense.get() : (float*)nullptr, c->dense_total, a.dense_off);
@@ -155,11 +160,11 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
     g.ACT = tt.act.get(); g.dACT = tt.dact.get(); g.red = tt.gred.get(); g.gslab = tt.gslab.get();
     g.gA = tl_gptr(c, tt, l.oA); g.gB = tl_gptr(c, tt, l.oB);
     g.up = a.up; g.Hv = a.Hv; g.Wv = a.Wv; g.has_gn = gn ? 1 : 0;
-    if (gn) {   // the activated input, recomputed (GroupNorm + SiLU + the step's dropout mask)
+    if (gn && want_p) {   // the activated input, recomputed (GroupNorm + SiLU + the step's dropout mask): only the weight gradient reads it
         ProfScope ps(c, s, "tb_act_kernel", 0);
         hipLaunchKernelGGL(tb_act_kernel, dim3(tb_blocks((long)NB * HWv * Cin)), dim3(RDMI_THREADS), 0, s, g);
     }
-    {   // weight gradient: K = samples x output pixels split into <= MAX_SPLIT chunks, slab summed in a fixed order
+    if (want_p) {   // weight gradient: K = samples x output pixels split into <= MAX_SPLIT chunks, slab summed in a fixed order
         TbGemmArgs w{};
         w.M = a.Cout; w.N = Cin; w.K = NB * HWo;
         w.Hv = a.Hv; w.Wv = a.Wv; w.Ho = a.Ho; w.Wo = a.Wo; w.stride = a.stride; w.pad = a.pad_lo; w.ntap = a.ntap; w.Cin = Cin; w.Cout = a.Cout;
@@ -179,7 +184,7 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
         hipLaunchKernelGGL(tb_wgrad_reduce_kernel, dim3(tb_blocks((long)a.ntap * a.Cout * Cin)), dim3(RDMI_THREADS), 0, s, (const float*)tt.wslab.get(), ns, a.ntap,
                            a.Cout, Cin, pgrad(b.pw[0]), pgrad(b.pw[1]), pgrad(b.pw[2]), b.co_blk, b.w_co, b.w_ci, b.w_t);
     }
-    if (l.in_is_x) return 0;                           // no gradient w.r.t. the network input
+    if (l.in_is_x) return grad_x ? launch_input_dgrad(c, G, 0, grad_x, NB, s) : 0;   // the network input: only on request
     {   // data gradient over the virtual input grid
         TbGemmArgs d{};
         d.M = NB * HWv; d.N = Cin; d.K = a.ntap * a.Cout;
@@ -196,9 +201,11 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
             ProfScope ps(c, s, "tb_gn_red_kernel", 0);
             hipLaunchKernelGGL(tb_gn_red_kernel, dim3((unsigned)a.G, (unsigned)NB), dim3(RDMI_THREADS), 0, s, g);
         }
-        ProfScope ps(c, s, "tb_rowsum_kernel", 0);
-        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 0, pgrad(b.pg));
-        hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 1, pgrad(b.pbeta));
+        if (want_p) {
+            ProfScope ps(c, s, "tb_rowsum_kernel", 0);
+            hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 0, pgrad(b.pg));
+            hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 1, pgrad(b.pbeta));
+        }
     }
     ProfScope ps(c, s, "tb_src_grad_kernel", 0);
     hipLaunchKernelGGL(tb_src_grad_kernel, dim3(tb_blocks((long)NB * a.Ha * a.Wa * Cin)), dim3(RDMI_THREADS), 0, s, g);
@@ -235,23 +242,23 @@ int tiled_attn_backward(rdmi_ctx* c, TiledTrain& tt, const rdmi_ctx::TLaunch& qk
     return 0;
 }
 
-int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grads_flat, size_t grads_numel, hipStream_t s) {
+int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grads_flat, size_t grads_numel, float* grad_x, hipStream_t s) {
     TiledTrain& tt = *T.tiled;
-    if (grads_numel != T.ptotal) return fail("grads buffer holds %zu floats, the model has %zu parameters", grads_numel, T.ptotal);
+    if (grads_flat && grads_numel != T.ptotal) return fail("grads buffer holds %zu floats, the model has %zu parameters", grads_numel, T.ptotal);
     const int NB = tt.last_B;
     if (NB < 1) return fail("rdmi_backward before rdmi_train_forward");
     const size_t NBmax = (size_t)c->max_batch;
     const int HW = c->H * c->W, Cc = c->arch.channels;
     // every parameter gradient below is a store; time_embed.W (not trained) stays zero.  The twin takes sums: zeroed (all of it,
     // t_ws_per_sample * max_batch floats -- the tensors are [tensor][sample] blocks, so the first NB samples are not one range)
-    HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
+    if (grads_flat) HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
     HIP_OK(hipMemsetAsync(tt.gws.get(), 0, c->t_ws_per_sample * NBmax * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
+    if (grads_flat) HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(tb_blocks((long)NB * HW * Cc)), dim3(RDMI_THREADS), 0, s, grad_out, tt.gfin.get(), NB, HW, Cc, 0);
     for (int li = (int)c->tl.size() - 1; li >= 0; --li) {
         const rdmi_ctx::TLaunch& l = c->tl[(size_t)li];
         if (l.kind == 0) {
-            if (int e = tiled_conv_backward(c, T, tt, l, tt.conv.at(li), grads_flat, NB, s)) return e;
+            if (int e = tiled_conv_backward(c, T, tt, l, tt.conv.at(li), grads_flat, grad_x, NB, s)) return e;
         } else if (l.kind == 2 && ends_with(l.name, ".pv")) {
             const std::string qk_name = l.name.substr(0, l.name.size() - 3) + ".qk";
             int qi = li - 1;
@@ -262,7 +269,7 @@ int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grad
         // kinds 1 / 5 (GroupNorm statistics): their gradient is part of the GroupNorm backward; 3 / 4 and `qk`: inside the attention backward
         HIP_OK(hipGetLastError());
     }
-    if (int e = embed_backward(c, T, grads_flat, NB, s)) return e;
+    if (grads_flat) { if (int e = embed_backward(c, T, grads_flat, NB, s)) return e; }
     if (c->profiling) prof_collect(c);
     return 0;
 }

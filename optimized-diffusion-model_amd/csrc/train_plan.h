@@ -53,10 +53,14 @@ struct TrainPlan {
     //      caller's x / sigma / labels / grad_out are copied into buffers of the plan first, the dropout seed is a device word.
     bool use_graph = true;
     hipStream_t cap = nullptr;                            // capture stream (the caller's may be the legacy default stream, which cannot capture)
-    hipGraphExec_t fwd_exec = nullptr, bwd_exec = nullptr;
-    std::vector<unsigned long long> fwd_key, bwd_key;     // what a recorded graph depends on (batch, dropout, pointers)
-    int fwd_calls = 0, bwd_calls = 0;                     // the first call of each runs eagerly (one-time attribute / table setup happens there)
+    // The backward has one recorded graph per mode (bit 0: grad_x requested, bit 1: parameter gradients requested): a replay writes
+    // exactly what that mode's recording wrote, and alternating modes (a training step, then a likelihood evaluation) keep replaying.
+    hipGraphExec_t fwd_exec = nullptr, bwd_exec[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<unsigned long long> fwd_key, bwd_key[4];  // what a recorded graph depends on (batch, dropout, pointers, mode)
+    int fwd_calls = 0, bwd_calls[4] = {0, 0, 0, 0};       // the first call of each runs eagerly (one-time attribute / table setup happens there)
     dev_ptr<float> x_in, out_buf, gout_buf, grads_int;    // grads_int: the flat parameter gradient the recorded backward writes
+    dev_ptr<float> gx_buf;                                // the input gradient the recorded backward writes (rdmi_backward_input)
+    long input_dgrad_calls = 0;                           // backward calls that ran the input data gradient (rdmi_path_info reports it)
     dev_ptr<unsigned long long> d_seed; pinned_ptr<unsigned long long> h_seed; int seed_slot = 0;   // device seed word; pinned staging ring of 64
     std::vector<PackJob> m_jobs_fwd, m_jobs_bwd;          // host mirrors of the two pack-job tables (uploaded only when a parameter pointer changed)
     long graph_replays = 0, graph_records = 0;
@@ -75,7 +79,23 @@ void conv_tile_cfg(ConvArgs& a, int& cfg) {
 int tiled_enable_training(rdmi_ctx* c, TrainPlan& T);
 int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* sigma, const float* labels, float* out, int B, float dropout_p,
                         uint64_t seed, hipStream_t s);
-int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grads_flat, size_t grads_numel, hipStream_t s);
+int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grads_flat, size_t grads_numel, float* grad_x, hipStream_t s);
+
+// grad_x = data gradient of input_conv from its scaled output gradient G [n][H*W][nf] (fp32, or bf16 on the bf16 layer plan)
+int launch_input_dgrad(rdmi_ctx* c, const float* G, int g_bf16, float* gx, int NB, hipStream_t s) {
+    InputDgradArgs a{};
+    a.G = G; a.W = P(c, "input_conv.weight"); a.gx = gx; a.NB = NB; a.H = c->H; a.Wd = c->W; a.C = c->arch.channels; a.Cout = c->arch.nf;
+    if (a.C > IDG_MAXC) return fail("input gradient: %d image channels (built for <= %d)", a.C, IDG_MAXC);
+    if (a.Cout % (g_bf16 ? 8 : 4)) return fail("input gradient: nf = %d is not a multiple of %d", a.Cout, g_bf16 ? 8 : 4);
+    const size_t lds = input_dgrad_lds_bytes(a.C, a.Cout);
+    if (lds > 64 * 1024) return fail("input gradient: %zu B of weights do not fit LDS", lds);
+    const dim3 grid((unsigned)(((long)NB * a.H * a.Wd + RDMI_THREADS / IDG_LANES - 1) / (RDMI_THREADS / IDG_LANES)));
+    ProfScope ps(c, s, "input_dgrad_kernel", 2.0 * NB * a.H * a.Wd * 9.0 * a.C * a.Cout);
+    if (g_bf16) hipLaunchKernelGGL(input_dgrad_kernel<true>, grid, dim3(RDMI_THREADS), lds, s, a);
+    else hipLaunchKernelGGL(input_dgrad_kernel<false>, grid, dim3(RDMI_THREADS), lds, s, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 
 // split the batch so that ~1000 workgroups exist whatever the layer's channel counts
 int launch_wgrad(WgradArgs w, hipStream_t s) {
@@ -330,6 +350,7 @@ int build_train_plan(rdmi_ctx* c, TrainPlan& T) {
         HIP_OK(hip_alloc(T.x_in, Mp * E));
         HIP_OK(hip_alloc(T.out_buf, Mp * E));
         HIP_OK(hip_alloc(T.gout_buf, Mp * E));
+        HIP_OK(hip_alloc(T.gx_buf, Mp * E));
         HIP_OK(hip_alloc(T.grads_int, std::max<size_t>(T.ptotal, 1)));
         HIP_OK(hip_alloc(T.d_seed, 8));
         HIP_OK(hipMemset(T.d_seed.get(), 0, 64));
@@ -619,15 +640,20 @@ int rdmi_train_forward(rdmi_ctx* c, const float* x, const float* sigma, const fl
     return 0;
 }
 
-// Backward of the last rdmi_train_forward: grad_out [B,1,H,W] -> every parameter gradient, written (not accumulated) into
-// grads_flat in the reference's parameter order (offsets = running sum of numel; time_embed.W stays zero).
-int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t grads_numel, const float* x, void* stream) {
-    if (!c || !grad_out || !grads_flat || !x) return fail("null argument");
+// Backward of the last rdmi_train_forward: grad_out [B,C,H,W] -> every parameter gradient, written (not accumulated) into
+// grads_flat in the reference's parameter order (offsets = running sum of numel; time_embed.W stays zero), and / or the gradient
+// w.r.t. the network input into grad_x.  grads_flat == NULL is the VJP-only mode: every launch that feeds only parameter gradients
+// (weight gradients and their side stream, bias / Dense_0 / gamma-beta sums, the embedding backward) is left out.
+int rdmi_backward_input(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t grads_numel, float* grad_x, const float* x, void* stream) {
+    if (!c || !grad_out || !x) return fail("null argument");
+    if (!grads_flat && !grad_x) return fail("rdmi_backward_input: neither grads_flat nor grad_x was given");
     TrainPlan* Tp = c->train.get();
     if (!Tp) return fail("call rdmi_enable_training first");
     TrainPlan& T = *Tp;
-    if (c->tiled) return tiled_backward(c, T, grad_out, grads_flat, grads_numel, (hipStream_t)stream);
-    if (grads_numel != T.ptotal) return fail("grads buffer holds %zu floats, the model has %zu parameters", grads_numel, T.ptotal);
+    if (grad_x) ++T.input_dgrad_calls;
+    if (c->tiled) return tiled_backward(c, T, grad_out, grads_flat, grads_numel, grad_x, (hipStream_t)stream);
+    const bool want_p = grads_flat != nullptr, want_x = grad_x != nullptr;
+    if (want_p && grads_numel != T.ptotal) return fail("grads buffer holds %zu floats, the model has %zu parameters", grads_numel, T.ptotal);
     hipStream_t s0 = (hipStream_t)stream;
     const int NB = T.last_B;
     const size_t NBmax = (size_t)c->max_batch;
@@ -644,11 +670,11 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
     auto body = [&](hipStream_t s) -> int {
     // transposed packs
     if (!T.jobs.empty()) hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)T.jobs.size()), dim3(RDMI_THREADS), 0, s, (const PackJob*)T.d_jobs.get());
-    HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
+    if (want_p) HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
     HIP_OK(hipMemsetAsync(T.gws.get(), 0, c->ws_per_sample * NBmax * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
+    if (want_p) HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
     auto gptr = [&](int t) -> float* { return t >= 0 ? T.gws.get() + c->tensors[(size_t)t].off * NBmax : nullptr; };
-    auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
+    auto pgrad = [&](int pi) -> float* { return (want_p && pi >= 0) ? grads_flat + T.poff[(size_t)pi] : nullptr; };   // VJP-only: null, the kernels drop that half
     static bool attr = false;
     if (!attr) {
         HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -680,7 +706,7 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
         const BwdConv& b2 = *bmap.at(oj);
         ColsumArgs ca{};
         ca.gY = o2.out_is_output ? grad_out : gptr(o2.out_tensor); ca.G = T.G[pj].get(); ca.gR = gptr(o2.tRes); ca.scale = o2.conv.out_scale;
-        ca.gdense = o2.use_dense ? T.gdense.get() : (float*)nullptr; ca.dense_stride = c->dense_total; ca.dense_off = o2.conv.dense_off;
+        ca.gdense = (want_p && o2.use_dense) ? T.gdense.get() : (float*)nullptr; ca.dense_stride = c->dense_total; ca.dense_off = o2.conv.dense_off;
         ca.db = pgrad(b2.p_b); ca.db2 = pgrad(b2.p_bsc); ca.HW = o2.conv.HWo; ca.C = o2.spec.Cout; ca.g_bf16 = sbf;
         return ca;
     };
@@ -690,7 +716,7 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
             AttnBwdArgs a{};
             a.x = op.attn.x; a.gOut = gptr(op.out_tensor); a.gX = gptr(op.tA);
             a.gamma = op.attn.gamma; a.beta = op.attn.beta;
-            a.dgamma = pgrad(c->pindex.at(op.name + ".GroupNorm_0.weight")); a.dbeta = pgrad(c->pindex.at(op.name + ".GroupNorm_0.bias"));
+            a.dgamma = pgrad(c->pindex.at(op.name + ".GroupNorm_0.weight")); a.dbeta = pgrad(c->pindex.at(op.name + ".GroupNorm_0.bias"));   // (all null in VJP-only mode)
             for (int k = 0; k < 4; ++k) {
                 const int pw = c->pindex.at(op.name + ".NIN_" + std::to_string(k) + ".W"), pb = c->pindex.at(op.name + ".NIN_" + std::to_string(k) + ".b");
                 a.W[k] = c->params[(size_t)pw].ptr; a.b[k] = c->params[(size_t)pb].ptr; a.dW[k] = pgrad(pw); a.db[k] = pgrad(pb);
@@ -729,12 +755,14 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
             ConvArgs d = b.dgrad; d.NB = NB; d.srcA = Gp;
             if (int e = launch_conv(b.dgrad_cfg, d, s)) return e;
         }
-        // GroupNorm / SiLU / dropout backward (+ materialise ACT for the weight gradient)
-        {
+        // the network input's gradient: input_conv has neither GroupNorm nor activation ahead of it, its data gradient is grad_x
+        if (want_x && op.a_is_input) { if (int e = launch_input_dgrad(c, Gp, sbf, T.gx_buf.get(), NB, s)) return e; }
+        // GroupNorm / SiLU / dropout backward (+ materialise ACT for the weight gradient); VJP-only: input_conv has nothing left to do here
+        if (want_p || b.has_dgrad || tail.G) {
             GnBwdArgs g{};
             g.srcA = op.a_is_input ? x : fa.srcA; g.srcB = fa.srcB; g.mapA = fa.mapA;
             g.CA = fa.CA; g.CB = fa.CB; g.Cv = fa.Cv; g.HWa = fa.HWa; g.HWv = fa.HWv; g.srcA_mod = 0; g.NB = NB;
-            g.GA = T.GA.get(); g.ACT = ACTp; g.a_bf16 = op.a_is_input ? 0 : sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
+            g.GA = T.GA.get(); g.ACT = want_p ? ACTp : nullptr; g.a_bf16 = op.a_is_input ? 0 : sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
             g.has_gn = b.has_gn ? 1 : 0; g.G = fa.G; g.eps = fa.eps;
             if (b.has_gn) { g.gamma = fa.gamma; g.beta = fa.beta; g.dgamma = pgrad(b.p_gamma); g.dbeta = pgrad(b.p_beta); }
             g.drop_p = op.dropout ? T.drop_p : 0.f; g.seed = T.seed; g.seed_dev = T.d_seed.get(); g.op_id = (uint32_t)oi;
@@ -754,14 +782,14 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
             GnBwdArgs g{};
             g.srcA = fa.scA; g.srcB = fa.scB; g.mapA = fa.mapSc;
             g.CA = fa.CscA; g.CB = fa.CscB; g.Cv = fa.Csc; g.HWa = fa.HWsa; g.HWv = fa.HWo; g.NB = NB;
-            g.GA = T.GS.get(); g.ACT = ACTSp; g.has_gn = 0; g.a_bf16 = sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
+            g.GA = T.GS.get(); g.ACT = want_p ? ACTSp : nullptr; g.has_gn = 0; g.a_bf16 = sbf; g.b_bf16 = sbf; g.s_bf16 = sbf;
             g.gA = gptr(op.tScA); g.gB = gptr(op.tScB);
             if (b.has_invS) { g.inv_start = T.d_int.get() + b.invS_start; g.inv_list = T.d_int.get() + b.invS_list; }
             g.tail = tail;
             hipLaunchKernelGGL(gn_bwd_kernel, dim3((unsigned)NB), dim3(GN_THREADS), gn_bwd_lds_bytes(fa.HWo, fa.Csc), s, g);
         }
         // weight gradients on the side stream (reference OIHW layout): dW[co][ci][t] += sum ACT[in(o,t)][ci] G[o][co];  NIN: dWn += Vs^T G
-        {
+        if (want_p) {
             WgradArgs w{};
             w.ACT = ACTp; w.G = Gp; w.dW = pgrad(b.p_w); w.tab = T.d_int.get() + b.wtab_off;
             w.NB = NB; w.HWv = fa.HWv; w.HWo = fa.HWo; w.Cin = Cin; w.Cout = sp.Cout; w.ntap = 9;
@@ -770,7 +798,7 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
             w.bf16 = sbf; w.s_bf16 = sbf;
             pending.push_back(w);
         }
-        if (b.has_sc) {
+        if (want_p && b.has_sc) {
             WgradArgs w{};
             const int Csc = sp.CscA + sp.CscB;
             w.ACT = ACTSp; w.G = Gp; w.dW = pgrad(b.p_wsc); w.tab = nullptr;
@@ -784,16 +812,24 @@ int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t 
     }
     if (int e = flush_wgrads(((nconv - 1) % (2 * grp)) / grp)) return e;
 
-    if (int e = embed_backward(c, T, grads_flat, NB, s)) return e;
+    if (want_p) { if (int e = embed_backward(c, T, grads_flat, NB, s)) return e; }
     if (T.two_streams)                                      // join: the caller's stream continues after the last weight gradients
         for (int p = 0; p < 2; ++p) if (done_rec[p]) HIP_OK(hipStreamWaitEvent(s, T.ev_done[p], 0));
     return 0;
     };   // body
     unsigned pb; std::memcpy(&pb, &T.drop_p, 4);
-    const std::vector<unsigned long long> key{(unsigned long long)NB, pb, param_ptr_hash(c)};
-    if (int e = run_recorded(T, T.bwd_exec, T.bwd_key, key, T.bwd_calls, s0, body)) return e;
-    HIP_OK(hipMemcpyAsync(grads_caller, T.grads_int.get(), T.ptotal * sizeof(float), hipMemcpyDeviceToDevice, s0));
+    const int mode = (want_x ? 1 : 0) | (want_p ? 2 : 0);
+    const std::vector<unsigned long long> key{(unsigned long long)NB, pb, param_ptr_hash(c), (unsigned long long)mode};
+    if (c->profiling && want_x) { if (int e = body(s0)) return e; prof_collect(c); }   // the input gradient's per-launch events: never from a recorded graph
+    else if (int e = run_recorded(T, T.bwd_exec[mode], T.bwd_key[mode], key, T.bwd_calls[mode], s0, body)) return e;
+    if (want_p) HIP_OK(hipMemcpyAsync(grads_caller, T.grads_int.get(), T.ptotal * sizeof(float), hipMemcpyDeviceToDevice, s0));
+    if (want_x) HIP_OK(hipMemcpyAsync(grad_x, T.gx_buf.get(), (size_t)NB * c->H * c->W * c->arch.channels * sizeof(float), hipMemcpyDeviceToDevice, s0));
     return 0;
+}
+
+int rdmi_backward(rdmi_ctx* c, const float* grad_out, float* grads_flat, size_t grads_numel, const float* x, void* stream) {
+    if (!grads_flat) return fail("null argument");
+    return rdmi_backward_input(c, grad_out, grads_flat, grads_numel, nullptr, x, stream);
 }
 
 // Diagnostic: how often the training step's launch graphs were recorded and replayed (tests: the recorded path is what runs).

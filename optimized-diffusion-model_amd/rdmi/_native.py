@@ -69,8 +69,10 @@ _PROTOS = {
     'rdmi_enable_training': ([C.c_void_p], C.c_int),
     'rdmi_train_forward': ([C.c_void_p, _F, _F, _F, _F, C.c_int, C.c_float, C.c_uint64, C.c_void_p], C.c_int),
     'rdmi_backward': ([C.c_void_p, _F, _F, C.c_size_t, _F, C.c_void_p], C.c_int),
+    'rdmi_backward_input': ([C.c_void_p, _F, _F, C.c_size_t, _F, _F, C.c_void_p], C.c_int),
     'rdmi_train_graph_stats': ([C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
     'rdmi_em_update': ([_F, _F, _F, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p], C.c_int),
+    'rdmi_pf_drift_div': ([_F, _F, _F, _F, _F, _F, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p], C.c_int),
     'rdmi_langevin_update': ([_F, _F, _F, _F, _F, _F, C.c_int, C.c_int, C.c_float, C.c_void_p], C.c_int),
     'rdmi_pc_sample': ([C.c_void_p, _F, _F, _F, _F, _F, _F, C.c_int, C.POINTER(PcOpts), C.c_uint, C.c_void_p], C.c_int),
     'rdmi_ode_sample': ([C.c_void_p, _F, _F, _F, C.c_int, C.POINTER(OdeOpts), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_uint, C.c_void_p], C.c_int),
@@ -223,9 +225,15 @@ class Context:
             check(lib().rdmi_train_forward(self._h, ptr(x), ptr(sigma), ptr(labels), ptr(out), x.shape[0], float(dropout_p),
                                            int(seed), stream_of(x)))
 
-    def backward(self, grad_out, grads_flat, x):
+    def backward(self, grad_out, grads_flat, x, grad_x=None):
+        """Backward of the last train_forward.  grads_flat: every parameter gradient (None with grad_x given: VJP-only mode, no
+        parameter gradient is computed); grad_x: the gradient w.r.t. the network input, like x."""
         with self._guard():
-            check(lib().rdmi_backward(self._h, ptr(grad_out), ptr(grads_flat), grads_flat.numel(), ptr(x), stream_of(x)))
+            if grad_x is None:
+                check(lib().rdmi_backward(self._h, ptr(grad_out), ptr(grads_flat), grads_flat.numel(), ptr(x), stream_of(x)))
+            else:
+                check(lib().rdmi_backward_input(self._h, ptr(grad_out), ptr(grads_flat), 0 if grads_flat is None else grads_flat.numel(),
+                                                ptr(grad_x), ptr(x), stream_of(x)))
 
     def train_graph_stats(self):
         """(recordings, replays) of the training step's launch graphs."""
@@ -422,6 +430,17 @@ def em_update(x, score, z, t, N, smin, smax):
     check(lib().rdmi_em_update(ptr(x.contiguous()), ptr(score.contiguous()), ptr(z.contiguous()), ptr(t.contiguous()),
                                ptr(x_out), ptr(x_mean), B, x.numel() // B, N, smin, smax, stream_of(x)))
     return x_out, x_mean
+
+
+def pf_drift_div(score, gx, eps, t, smin, smax):
+    """Right-hand side of the likelihood ODE for RVESDE: (drift like score, div [B]) from the score, its VJP gx and the probe eps."""
+    require_device(score)
+    B = score.shape[0]
+    drift = torch.empty_like(score, dtype=torch.float32)
+    div = torch.empty(B, dtype=torch.float32, device=score.device)
+    check(lib().rdmi_pf_drift_div(ptr(score.contiguous()), ptr(gx.contiguous()), ptr(eps.contiguous()), ptr(t.contiguous().float()),
+                                  ptr(drift), ptr(div), B, score.numel() // B, float(smin), float(smax), stream_of(score)))
+    return drift, div
 
 
 def langevin_update(x, score, z, snr):

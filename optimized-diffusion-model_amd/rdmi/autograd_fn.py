@@ -1,8 +1,9 @@
 """torch.autograd glue for the HIP training step: NCSNpp forward/backward and the score-matching loss.
 
 No arithmetic here: forward = rdmi_train_forward (layer plan, activations kept, Dropout_0 by in-kernel Philox),
-backward = rdmi_backward (every parameter gradient into one flat buffer in the reference's parameter order, handed
-to autograd as views).  The dropout seed of a step is drawn from the torch generator, so torch.manual_seed controls it.
+backward = rdmi_backward / rdmi_backward_input (every parameter gradient into one flat buffer in the reference's parameter order,
+handed to autograd as views; the input gradient when x requires it; no parameter gradient at all when no parameter requires one).
+The dropout seed of a step is drawn from the torch generator, so torch.manual_seed controls it.
 """
 import torch
 
@@ -31,15 +32,19 @@ class _NCSNppFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         model = ctx.model
         plist = ctx.plist
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        if not any(ctx.needs_input_grad[4:]):                          # frozen parameters: VJP-only backward
+            ctx.tctx.backward(gout.contiguous().float(), None, x, grad_x=gx)
+            return (None, gx, None, None, *([None] * len(plist)))
         total = getattr(model, '_n_param_elems', None)
         if total is None:
             total = model._n_param_elems = sum(p.numel() for p in plist)
         flat = torch.empty(total, dtype=torch.float32, device=x.device)
-        ctx.tctx.backward(gout.contiguous().float(), flat, x)
+        ctx.tctx.backward(gout.contiguous().float(), flat, x, grad_x=gx)
         # one C++ call makes the 260 views (fresh tensor objects: autograd adopts them as .grad without a copy)
         views = torch._utils._unflatten_dense_tensors(flat, plist)
         grads = [v if p.requires_grad else None for v, p in zip(views, plist)]
-        return (None, None, None, None, *grads)
+        return (None, gx, None, None, *grads)
 
 
 def ncsnpp_apply(model, x, time_cond, class_labels):

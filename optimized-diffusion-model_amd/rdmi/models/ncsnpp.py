@@ -262,6 +262,20 @@ class NCSNpp(nn.Module):
                      float(sigma_min), float(sigma_max))
         return out
 
+    def native_vjp(self, x, sigma, class_labels, cotangent):
+        """-> (out, gx): out = model(x, sigma, class_labels) without dropout and gx = d<cotangent, out>/dx, by the train-mode forward
+        (p = 0) and the VJP-only backward (no parameter gradient is computed).  No autograd objects: for callers that need speed
+        (rdmi.likelihood)."""
+        x = self._prep(x)
+        if self.conditional and class_labels is None:
+            raise RuntimeError('class_labels is required: the model is conditional (label_emb)')
+        tctx = self.train_context(x.shape[0], x.shape[2], x.shape[3], x.device)
+        out, gx = torch.empty_like(x), torch.empty_like(x)
+        lab = None if class_labels is None else class_labels.contiguous().float()
+        tctx.train_forward(x, sigma.contiguous().float(), lab, out, 0.0, 0)
+        tctx.backward(cotangent.contiguous().float(), None, x, grad_x=gx)
+        return out, gx
+
     # ------------------------------------------------------------------ nn.Module surface
     def forward(self, x, time_cond, class_labels=None):
         """RD/models/ncsnpp.py:226-354."""
@@ -269,7 +283,8 @@ class NCSNpp(nn.Module):
             # label drop for classifier-free guidance (:242-246): a [B] Bernoulli mask on the labels
             mask = (torch.rand(x.shape[0], device=x.device) < self.cond_drop_prob).float().unsqueeze(1)
             class_labels = class_labels * (1 - mask)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # (also a frozen model with a differentiable input, in eval mode too: dropout is 0 there)
             from .. import autograd_fn
             return autograd_fn.ncsnpp_apply(self, x, time_cond, class_labels)
         if self.training and self.dropout > 0:
