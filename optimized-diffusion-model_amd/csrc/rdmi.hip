@@ -724,7 +724,12 @@ struct TiledBuilder {
     // AttnBlockpp (RD/models/layerspp.py:67-96): GN -> q,k,v (one 1x1 conv, Cout = 3C) -> softmax(q k^T / sqrt(C)) v -> NIN_3 -> (x + h)/sqrt2
     TT attn(const std::string& name, const TT& x) {
         const int C = x.C, Lq = x.H * x.W;
-        if (C % 32 != 0 || Lq % 16 != 0) throw std::runtime_error("tiled attention needs C % 32 == 0 and H*W % 16 == 0");
+        // C % 32: the q | k | v pack is laid out with K = C unpadded while the 1x1 conv contracts pad32(C) channels.  L = H*W % 16: Q K^T
+        // contracts K = C and P V contracts K = L; bgemm_nt_kernel steps K by 16 and bgemm_nt_bf16_kernel takes any K % 8 == 0 (its last
+        // 32-step is predicated), the row / column tails of both are clamped and masked.  The fused bf16 core has its own rule below
+        // (C of 64 / 128 / 256 and L % 64 == 0) and every other bf16 shape takes the bgemm route.
+        if (C % 32 != 0 || Lq % 16 != 0)
+            throw std::runtime_error(name + ": tiled attention needs C % 32 == 0 and H*W % 16 == 0 (C = " + std::to_string(C) + ", H*W = " + std::to_string(Lq) + ")");
         TT st = stats(name + ".GroupNorm_0", x, nullptr);
         const size_t o3 = b.alloc_w(bf16() ? (size_t)3 * C * C / 2 : (size_t)3 * C * C);
         for (int i = 0; i < 3; ++i) {
@@ -916,6 +921,17 @@ int build_plan(rdmi_ctx* c) {
     const rdmi_arch& a = c->arch;
     Layout L = build_layout(c);
     build_params(c, L);
+    // every GroupNorm has G = min(C / 4, 32) groups (RD/models/layerspp.py) and every plan computes Cg = C / G: a C that G does not divide
+    // (nf 48 with ch_mult [1, 2, 2]: the 144-channel concat, G = 32) is refused by torch.nn.GroupNorm and would silently drop channels here
+    for (const Param& p : c->params) {
+        const bool gn_w = p.name == "out_norm.weight" || (p.name.find(".GroupNorm_") != std::string::npos && p.name.size() > 7 &&
+                                                          p.name.compare(p.name.size() - 7, 7, ".weight") == 0);
+        if (!gn_w) continue;
+        const int C = (int)p.numel, G = std::min(C / 4, 32);
+        if (G < 1 || C % G != 0)
+            return fail("%s: GroupNorm over %d channels in min(C / 4, 32) = %d groups: num_channels must be divisible by num_groups",
+                        p.name.substr(0, p.name.size() - 7).c_str(), C, G);
+    }
     Builder b{c};
     int err = 0;
     // Dense_0 offsets in block order (down, mid1, mid2, up)

@@ -870,7 +870,10 @@ __global__ __launch_bounds__(RDMI_THREADS) void bgemm_nt_kernel(BgemmArgs a) {
     }
 }
 
-// bf16 variant: the fp32 operands are rounded to bf16 as they are loaded (8 consecutive k per lane), fp32 accumulate.  K % 32 == 0.
+// bf16 variant: the fp32 operands are rounded to bf16 as they are loaded (8 consecutive k per lane), fp32 accumulate.  K % 8 == 0:
+// the MFMA contracts 32 k per step, and in a last step with fewer left (attention over L = 144 or 16 positions: P V has K = L) the
+// lanes whose 8 k lie at or beyond K take zero operands WITHOUT loading (those addresses are the next row's, or past the tensor).
+// The full steps are the same instructions in the same order as before: nothing changes for K % 32 == 0.
 __global__ __launch_bounds__(RDMI_THREADS) void bgemm_nt_bf16_kernel(BgemmArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lrow = lane & 15, kq = lane >> 4;
@@ -887,10 +890,23 @@ __global__ __launch_bounds__(RDMI_THREADS) void bgemm_nt_bf16_kernel(BgemmArgs a
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < a.K; k += 32) {
+    const int Kfull = a.K & ~31;
+    for (int k = 0; k < Kfull; k += 32) {
         const u32x4 af = frag(Ap + k);
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = mfma16_bf16(af, frag(Bp[t] + k), acc[t]);
+    }
+    if (Kfull < a.K) {
+        const bool live = Kfull + kq * 8 < a.K;
+        const u32x4 zero{0u, 0u, 0u, 0u};
+        u32x4 af = zero, bfr[4] = {zero, zero, zero, zero};
+        if (live) {
+            af = frag(Ap + Kfull);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) bfr[t] = frag(Bp[t] + Kfull);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = mfma16_bf16(af, bfr[t], acc[t]);
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

@@ -53,8 +53,13 @@ def _attn(p, pre, x):
     return (x + _nin(h, p, pre + '.NIN_3')) / math.sqrt(2.)
 
 
-def ncsnpp_forward(p, x, sigma, labels, ch_mult=(1, 2, 2), nrb=2, attn_levels=(True, False, False), scale_by_sigma=False):
-    """NCSNpp.forward, eval mode (RD/models/ncsnpp.py:226-354); scale_by_sigma: h / time_cond (:350-351)."""
+def ncsnpp_forward(p, x, sigma, labels, ch_mult=(1, 2, 2), nrb=2, attn_levels=(True, False, False), scale_by_sigma=False, taps=None):
+    """NCSNpp.forward, eval mode (RD/models/ncsnpp.py:226-354); scale_by_sigma: h / time_cond (:350-351).
+    taps: an optional dict that receives every block's output under the block's state-dict prefix ('down_blocks.1', 'up_attn.3', ...)."""
+    def tap(name, h):
+        if taps is not None:
+            taps[name] = h
+        return h
     xp = (torch.log(sigma)[:, None] * p['time_embed.W'][None, :]) * 2 * math.pi
     temb = torch.cat([torch.sin(xp), torch.cos(xp)], dim=-1)
     temb = F.linear(F.silu(F.linear(temb, p['time_mlp.0.weight'], p['time_mlp.0.bias'])), p['time_mlp.2.weight'], p['time_mlp.2.bias'])
@@ -64,23 +69,23 @@ def ncsnpp_forward(p, x, sigma, labels, ch_mult=(1, 2, 2), nrb=2, attn_levels=(T
     hs, d, nlev = [h], 0, len(ch_mult)
     for i in range(nlev):
         for _ in range(nrb):
-            h = _resblock(p, f'down_blocks.{d}', h, ta)
+            h = tap(f'down_blocks.{d}', _resblock(p, f'down_blocks.{d}', h, ta))
             if attn_levels[i]:
-                h = _attn(p, f'down_attn.{d}', h)
+                h = tap(f'down_attn.{d}', _attn(p, f'down_attn.{d}', h))
             hs.append(h); d += 1
         hs.append(h)
         if i != nlev - 1:
             h = F.conv2d(F.pad(h, (0, 1, 0, 1)), p[f'downsample.{i}.Conv_0.weight'], p[f'downsample.{i}.Conv_0.bias'], stride=2)
-    h = _resblock(p, 'mid_block2', _resblock(p, 'mid_block1', h, ta), ta)
+    h = tap('mid_block2', _resblock(p, 'mid_block2', tap('mid_block1', _resblock(p, 'mid_block1', h, ta)), ta))
     u = 0
     for i in range(nlev):
         for _ in range(nrb + 1):
             sk = hs.pop()
             if h.shape[2:] != sk.shape[2:]:
                 h = F.interpolate(h, size=sk.shape[2:], mode='nearest')
-            h = _resblock(p, f'up_blocks.{u}', torch.cat([h, sk], dim=1), ta)
+            h = tap(f'up_blocks.{u}', _resblock(p, f'up_blocks.{u}', torch.cat([h, sk], dim=1), ta))
             if attn_levels[nlev - 1 - i]:
-                h = _attn(p, f'up_attn.{u}', h)
+                h = tap(f'up_attn.{u}', _attn(p, f'up_attn.{u}', h))
             u += 1
         if i != nlev - 1:
             h = F.interpolate(h, scale_factor=2, mode='nearest')

@@ -35,6 +35,11 @@ def small_rgb_model(ge):
 def make_case(case, dev, B=None):
     """-> (model, params, arch, (x, sigma, lab, gout) on `dev`, (sigma_min, sigma_max))."""
     import __graft_entry__ as ge
+    if case in ('S1', 'S2', 'S3', 'S4'):            # the shape matrix of tests/tiled_shapes.py
+        from tests import tiled_shapes
+        model, params, arch, args, sig = tiled_shapes.grad_case(case, dev)
+        model.eval()
+        return model, params, arch, args, sig
     if case.startswith('layer'):
         model, _, params = ge.make_model(dev)
         if case == 'layer_bf16':

@@ -76,6 +76,11 @@ def test_unsupported_configs_fail_loudly():
     cfg = ge.demo_config(); cfg.model.embedding_type = 'positional'
     with pytest.raises(NotImplementedError, match='fourier'):
         mutils.create_model(cfg)
+    # a GroupNorm whose min(C / 4, 32) groups do not divide C (the 144-channel concatenation of nf 48, ch_mult [1, 2, 2]): torch refuses the
+    # shell here, rdmi_create refuses the same architecture through the C ABI (tests/test_emu_tiled_shapes.py)
+    cfg = ge.demo_config(); cfg.model.nf, cfg.model.num_res_blocks = 48, 1
+    with pytest.raises(ValueError, match='divisible'):
+        mutils.create_model(cfg)
 
 
 def test_ema_matches_reference_formula():
