@@ -247,6 +247,16 @@ const char* rdmi_path_info(rdmi_ctx* ctx);
  * during the last forward, with a one-line description per op.  Returns the op count. */
 int rdmi_debug_op_cycles(rdmi_ctx* ctx, long long* host_cycles, int cap, const char** desc, int desc_cap);
 
+/* Diagnostic: the fused programs of the context, in the order they were built (inference programs first; a training forward, if enabled,
+ * last).  Returns the op count of program `prog` with one description line per op, its samples per workgroup and whether it is the
+ * co-operative / the training program; -1 when there is no such program. */
+int rdmi_debug_program(rdmi_ctx* ctx, int prog, int* S, int* coop, int* train, const char** desc, int desc_cap);
+
+/* Diagnostic: copy `numel` floats of the packed-weight arena, from the start of the packed tensor `key` on (a conv's module name, e.g.
+ * "down_blocks.0.Conv_0"; "<upsample conv>.up4": the 4 phases x 4 pre-summed taps of the folded upsample conv), to the device buffer dst.
+ * Packed tensors are current after rdmi_repack or any forward. */
+int rdmi_debug_packed(rdmi_ctx* ctx, const char* key, float* dst, size_t numel, void* stream);
+
 /* Diagnostic: has any co-operative launch of this context (groups of four workgroups sharing the low-resolution section of the
  * fused U-Net: DESIGN.md 4.2d) given up one of its bounded inter-workgroup waits?  *gave_up = 0: never; 1: yes -- the output
  * samples of the affected workgroups were overwritten with NaN by the kernel itself; from then on the context stops selecting the

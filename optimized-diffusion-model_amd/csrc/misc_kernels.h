@@ -18,7 +18,9 @@ struct PackJob {
     int ntap;
     long s_co, s_ci, s_t;     // source strides (elements) of output channel, input channel, tap
     int kind;                 // 0: pack weights, 1: plain copy of Cout floats to dst + n_off, 2: pack weights as bf16 [tap][K/32][Npad][32],
-                              // 3: pack the PRODUCT src (W [Cin][Cout], NIN layout) x src2 (W [Cout][Cout]), 4: the vector src (Cout floats) x src2 -> dst + n_off
+                              // 3: pack the PRODUCT src (W [Cin][Cout], NIN layout) x src2 (W [Cout][Cout]), 4: the vector src (Cout floats) x src2 -> dst + n_off,
+                              // 5: a 3x3 conv that follows a nearest x2 upsample as four 2x2 convs on the source grid: ntap = 16 blocks [phase 2py+px][tap 2ty+tx],
+                              //    each the sum of the 3x3 taps that read that source pixel (rdmi.hip: FusedBuilder::conv_up4)
     const float* src2;        // kinds 3 / 4: the right-hand factor (a NIN weight [in][out])
     int col_il;               // kind 2, tiled plan: 0 / 1 none; F = 2 / 4: destination columns are interleaved within groups of 16 F -- column g sits at
                               // position (g / 16F) * 16F + (g % F) * 16 + (g % 16F) / F, so that lane l of the F adjacent 16-column MFMA tiles of a
@@ -73,6 +75,18 @@ __global__ __launch_bounds__(RDMI_THREADS) void pack_kernel(const PackJob* __res
         if (co < j.Cout && ci < j.Cin) {
             if (j.kind == 3) {                            // (W W2)[ci][co]; the middle dimension is W's output = W2's input = Cout channels
                 for (int k = 0; k < j.Cout; ++k) v = fmaf(j.src[(long)ci * j.s_ci + k * j.s_co], j.src2[(long)k * j.Cout + co], v);
+            } else if (j.kind == 5) {                     // t = 4 * phase + tap of the folded upsample conv: the 3x3 taps that read this phase's source pixel, summed
+                const int py = t >> 3, px = (t >> 2) & 1, ty = (t >> 1) & 1, tx = t & 1;
+                const int ky0 = ty * (1 + py), ky1 = ky0 + 1 + (py != ty);      // py 0: {0}, {1, 2};  py 1: {0, 1}, {2}
+                const int kx0 = tx * (1 + px), kx1 = kx0 + 1 + (px != tx);
+                const float* const s = j.src + co * j.s_co + ci * j.s_ci;
+                bool first = true;
+                for (int ky = ky0; ky < ky1; ++ky)        // fixed order: ky ascending, then kx
+                    for (int kx = kx0; kx < kx1; ++kx) {
+                        const float wv = s[(ky * 3 + kx) * j.s_t];
+                        v = first ? wv : v + wv;
+                        first = false;
+                    }
             } else v = j.src[co * j.s_co + ci * j.s_ci + t * j.s_t];
         }
         j.dst[(((long)t * (j.Kpad >> 4) + ch) * j.Npad + j.n_off + co) * 16 + kk] = v;

@@ -348,6 +348,14 @@ void build_params(rdmi_ctx* c, const Layout& L) {
 // ------------------------------------------------------------------------------------------
 // plan builder
 // ------------------------------------------------------------------------------------------
+// Shapes for which the 3x3 conv after a nearest-x2 upsample runs folded into four 2x2 phase convs in the inference programs of the
+// workgroup-resident kernel (FusedBuilder::conv_up4): a 4x4 source (a phase = one 16-row MFMA tile), a square weight, input channels in
+// whole groups of 128 (the single-tile tap-major loop with the 8-deep weight ring).  RDMI_NO_UP_FOLD=1 keeps the nine-tap op everywhere.
+// Asked by the layer plan (does the folded packing exist?) and by the program builder (does this op fold?): one rule for both.
+inline bool up_fold_shape_ok(int Hs, int Ws, int Cin, int Cout) {
+    return std::getenv("RDMI_NO_UP_FOLD") == nullptr && Hs * Ws == 16 && Cin == Cout && Cin % 128 == 0;
+}
+
 struct Builder {
     rdmi_ctx* c;
     std::vector<int> ints;       // table / map arena (host)
@@ -1023,6 +1031,13 @@ int build_plan(rdmi_ctx* c) {
             s.conv = s.name + ".Conv_0"; s.Ho = 2 * H; s.Wo = 2 * W; s.Cout = ch;
             h = b.add_conv(s, &err);
             if (err) return err;
+            if (k == a.n_levels - 2 && up_fold_shape_ok(H, W, ch, ch)) {      // the upsample onto level 0, folded: 4 phases x 4 pre-summed taps (inference programs of the workgroup-resident kernel)
+                const int Kp = pad16(ch), Np = pad16(ch);
+                const size_t o = b.alloc_w((size_t)16 * Kp * Np);
+                b.job_pack(s.conv + ".weight", o, ch, ch, Kp, Np, 0, 16, (long)ch * 9, 9, 1);
+                c->jobs.back().kind = 5;
+                c->wmap[s.conv + ".up4"] = o;
+            }
             H *= 2; W *= 2;
         }
     }
@@ -1113,7 +1128,10 @@ struct FusedBuilder {
     std::map<std::string, int> tabcache;       // geometry key -> encoded table reference (region << 24 | offset in shorts)
     std::vector<short> tabs1;                  // region 1: tables of the multi-sample (low-resolution) section, resident in LDS only during it
     int tab1_lds = 0;                          // LDS byte offset of region 1 (an arena block of the low-resolution section)
-    struct LT { int off = -1, C = 0, H = 0, W = 0, rs = 0, bytes = 0, ns = 1; int hw() const { return H * W; } int rows() const { return ns * H * W; } };
+    struct LT { int off = -1, C = 0, H = 0, W = 0, rs = 0, bytes = 0, ns = 1; bool pm = false; int hw() const { return H * W; } int rows() const { return ns * H * W; } };
+    // pm: the rows are PHASE-MAJOR (output of the folded upsample conv, conv_up4): pixel (2y + py, 2x + px) of the H x W grid sits in row
+    // (2 py + px) * (H/2 * W/2) + y * W/2 + x.  Readers go through a row map (gather_cat) -- no op takes such a tensor as a plain grid.
+    static int pm_row(int H, int W, int y, int x) { return (2 * (y & 1) + (x & 1)) * ((H / 2) * (W / 2)) + (y / 2) * (W / 2) + x / 2; }
     int S = 1;                      // samples per workgroup of the program being built
     bool coop = false;              // co-operative program: S = 4 samples per GROUP of four workgroups (unet_kernel.h: fop_conv_coop)
     bool train = false;             // training forward: stash every layer-plan tensor, Dropout_0 in the fused GroupNorm_1 epilogues
@@ -1215,16 +1233,31 @@ struct FusedBuilder {
         for (int m = 0; m < M; ++m) v[(size_t)m] = (short)m;
         return add_table("id:" + std::to_string(M), v);
     }
-    int map_table(int Hs, int Ws, int Hd, int Wd) {      // nearest map as a GATHER row map
+    int map_table(int Hs, int Ws, int Hd, int Wd, bool pm = false) {      // nearest map as a GATHER row map (pm: onto a phase-major source, LT::pm)
         std::vector<short> v((size_t)Hd * Wd);
         for (int y = 0; y < Hd; ++y)
             for (int x = 0; x < Wd; ++x) {
                 const int sy = std::min((int)std::floor(y * ((float)Hs / Hd)), Hs - 1);
                 const int sx = std::min((int)std::floor(x * ((float)Ws / Wd)), Ws - 1);
-                v[(size_t)y * Wd + x] = (short)(sy * Ws + sx);
+                v[(size_t)y * Wd + x] = (short)(pm ? pm_row(Hs, Ws, sy, sx) : sy * Ws + sx);
             }
         char key[64];
-        snprintf(key, sizeof key, "map:%d,%d,%d,%d", Hs, Ws, Hd, Wd);
+        snprintf(key, sizeof key, "map:%d,%d,%d,%d,%d", Hs, Ws, Hd, Wd, pm ? 1 : 0);
+        return add_table(key, v);
+    }
+    // Tap table t = 2 ty + tx of the folded upsample conv over a source of Hs x Ws = 16 pixels: entry [16 p + i] is the source row that tap
+    // (ty, tx) of phase p = 2 py + px reads for source pixel i = y * Ws + x, i.e. pixel (y + ty - 1 + py, x + tx - 1 + px), or -1 (zero row).
+    // An upsampled pixel lies outside the 2Hs x 2Ws grid exactly when its source pixel lies outside Hs x Ws: the padding carries over.
+    int up4_table(int Hs, int Ws, int tap) {
+        std::vector<short> v((size_t)4 * Hs * Ws, (short)-1);
+        for (int p = 0; p < 4; ++p)
+            for (int y = 0; y < Hs; ++y)
+                for (int x = 0; x < Ws; ++x) {
+                    const int sy = y + (tap >> 1) - 1 + (p >> 1), sx = x + (tap & 1) - 1 + (p & 1);
+                    if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) v[(size_t)p * Hs * Ws + y * Ws + x] = (short)(sy * Ws + sx);
+                }
+        char key[64];
+        snprintf(key, sizeof key, "up4:%d,%d,%d", Hs, Ws, tap);
         return add_table(key, v);
     }
 
@@ -1276,12 +1309,14 @@ struct FusedBuilder {
         FOp o = blank(FOP_GATHER);
         o.dst_off = dst.off; o.dst_rs = dst.rs; o.rows = dst.rows(); o.C = dst.C;
         o.CA = A.C; o.CB = CB; o.a_off = A.off; o.a_rs = A.rs; o.a_hw = A.hw(); o.hw_shift = shift_of(dst.hw());
-        if (A.H != dst.H || A.W != dst.W) o.a_map_off = map_table(A.H, A.W, dst.H, dst.W);
+        if (A.H != dst.H || A.W != dst.W || A.pm) o.a_map_off = map_table(A.H, A.W, dst.H, dst.W, A.pm);
+        if (A.pm && A.ns != 1) fail_("phase-major tensors are single-sample");
         o.b_off = -1;
         const int idx = emit(o);
         spill_fix.push_back({idx, spillB, 1});
     }
     void copy_t(const LT& dst, const LT& src) {
+        if (src.pm) fail_("copy of a phase-major tensor");
         FOp o = blank(FOP_GATHER);
         o.dst_off = dst.off; o.dst_rs = dst.rs; o.rows = dst.rows(); o.C = dst.C;
         o.CA = src.C; o.CB = 0; o.a_off = src.off; o.a_rs = src.rs; o.a_hw = src.hw(); o.hw_shift = shift_of(dst.hw());
@@ -1293,6 +1328,7 @@ struct FusedBuilder {
     std::vector<size_t> slot_log; size_t slot_pos = 0; bool slot_replay = false;
     std::vector<SpillFix> spill_fix;
     size_t spill_store(const LT& t) {            // LDS tensor -> this workgroup's slot of the spill buffer
+        if (t.pm) fail_("spill of a phase-major tensor");
         FOp o = blank(FOP_STORE);
         o.dst_off = t.off; o.dst_rs = t.rs; o.rows = t.rows(); o.C = t.C; o.hw_shift = shift_of(t.hw());
         const int idx = emit(o);
@@ -1341,6 +1377,7 @@ struct FusedBuilder {
         return true;
     }
     void gn(const LT& t, const std::string& pre, bool act, const LT* src = nullptr) {
+        if (t.pm || (src && src->pm)) fail_("GroupNorm of a phase-major tensor");
         if (try_fuse_gn(t, pre, act, src)) return;
         if (train && pre.size() > 12 && pre.compare(pre.size() - 12, 12, ".GroupNorm_1") == 0) fail_("training forward: " + pre + " is not folded into its conv (Dropout_0 lives in that epilogue)");
         ++n_gn_ops;
@@ -1373,6 +1410,7 @@ struct FusedBuilder {
              const std::string& bias2_param) {
         FOp o = blank(FOP_CONV);
         const int ns = ns_now();
+        if (in.pm || (resid && resid->pm) || (dst && dst->pm)) fail_("conv over a phase-major tensor");
         o.rows = ns * Ho * Wo; o.mtiles = pad16(o.rows) / 16; o.Cout = Cout; o.Cout_pad = pad16(Cout);
         o.ntap = ntap; o.hw_shift = shift_of(Ho * Wo);
         if (ns > 1 && dst_kind != 0) fail_("multi-sample convs write LDS tensors only");
@@ -1420,6 +1458,34 @@ struct FusedBuilder {
                 fail_("co-operative conv shape (Cout " + std::to_string(Cout) + ", " + std::to_string(q.mtiles) + " row tiles, " + std::to_string(q.main_ph.nch) + " chunks)");
             if (ntap == 9) { pendx.on = true; pendx.t = *dst; }      // the next conv contracts over this tensor: all-gather it
         }
+        return idx;
+    }
+    // Can the 3x3 conv over the nearest-x2 upsampled `in` run folded (conv_up4)?  Inference programs only: the training backward needs the
+    // unfolded weight gradient.  RDMI_NO_UP_FOLD=1 keeps the nine-tap op (A/B and debugging).
+    bool up_fold_ok(const LT& in, int Hv, int Wv, int Cout) const {
+        return !train && cur_samp >= 0 && !in.pm && Hv == 2 * in.H && Wv == 2 * in.W && up_fold_shape_ok(in.H, in.W, in.C, Cout) &&
+               c->wmap.count("upsample." + std::to_string(c->arch.n_levels - 2) + ".Conv_0.up4") != 0;
+    }
+    // The same conv as FOUR 2x2 convs on the source grid, one per output phase (py, px): output pixel (2y + py, 2x + px) reads source rows
+    // y - 1, y, y through the nearest map when py = 0 and y, y, y + 1 when py = 1 (columns alike), so the taps that share a source pixel
+    // have their weights summed once at repack time (pack kind 5) -- 4 taps instead of 9.  Each phase is one 16-row tile with its own four
+    // weight blocks (FOp::w_tile_stride); dst is written phase-major (LT::pm).
+    int conv_up4(const LT& in, const std::string& wkey, int Cout, const std::string& bias_param, LT* dst) {
+        FOp o = blank(FOP_CONV);
+        o.rows = 4 * in.hw(); o.mtiles = 4; o.Cout = Cout; o.Cout_pad = pad16(Cout);
+        o.ntap = 4; o.hw_shift = shift_of(o.rows);
+        o.main_ph.lds_off = in.off; o.main_ph.rs = in.rs; o.main_ph.nch = in.C / 16;
+        for (int t = 0; t < 4; ++t) o.tab_off[t] = up4_table(in.H, in.W, t);
+        o.w_tile_stride = 4 * in.C * o.Cout_pad * (int)sizeof(float);
+        o.dst_off = dst->off; o.dst_rs = dst->rs;
+        // fop_conv honours w_tile_stride only where a single-tile pass takes fconv_main_t<.., 1, false, 8>: chunks per tap in whole eights, more
+        // than 4 rows, a plain LDS destination; the packed block is square (kind 5 packs ch x ch)
+        if (o.main_ph.nch % 8 != 0 || o.rows <= 4 || o.dst_kind != 0 || in.C != Cout || in.hw() != 16 || in.pm || cur_samp < 0 || dst->C != Cout || dst->hw() != o.rows)
+            fail_("folded upsample conv: unsupported shape (" + std::to_string(in.H) + "x" + std::to_string(in.W) + " source, " + std::to_string(in.C) + " -> " + std::to_string(Cout) + " channels)");
+        dst->pm = true;
+        const int idx = emit(o);
+        patch_arena(idx, F_W, c->wmap.at(wkey + ".up4"));
+        patch_param(idx, F_BIAS, bias_param);
         return idx;
     }
 };
@@ -1729,7 +1795,8 @@ int build_fused_program_pass(rdmi_ctx* c, rdmi_ctx::FusedProg& q, int S, int TAB
         if (nlev > 1) {                                // the upsample conv onto level 0's (even) grid
             LT o = b.talloc(ch, 2 * H, 2 * W);
             const std::string nm = "upsample." + std::to_string(nlev - 2) + ".Conv_0";
-            b.conv(h, 2 * H, 2 * W, 2 * H, 2 * W, 1, 1, 9, nm, 0, ch, nm + ".bias", 0, 0, &o, 1.f, -1, nullptr, nullptr, "", "");
+            if (b.up_fold_ok(h, 2 * H, 2 * W, ch)) b.conv_up4(h, nm, ch, nm + ".bias", &o);
+            else b.conv(h, 2 * H, 2 * W, 2 * H, 2 * W, 1, 1, 9, nm, 0, ch, nm + ".bias", 0, 0, &o, 1.f, -1, nullptr, nullptr, "", "");
             b.tfree(h);
             h = o; H *= 2; W *= 2;
         }
@@ -2262,6 +2329,26 @@ int rdmi_debug_op_cycles(rdmi_ctx* c, long long* host, int cap, const char** des
     }
     for (int i = 0; i < n && i < desc_cap; ++i) desc[i] = q0.fdesc[(size_t)i].c_str();
     return n;
+}
+
+int rdmi_debug_program(rdmi_ctx* c, int prog, int* S, int* coop, int* train, const char** desc, int desc_cap) {
+    if (!c || prog < 0 || prog >= (int)c->progs.size() || !c->progs[(size_t)prog].ok) return -1;
+    const rdmi_ctx::FusedProg& q = c->progs[(size_t)prog];
+    if (S) *S = q.S;
+    if (coop) *coop = q.coop ? 1 : 0;
+    if (train) *train = q.train ? 1 : 0;
+    const int n = (int)q.fdesc.size();
+    for (int i = 0; desc && i < n && i < desc_cap; ++i) desc[i] = q.fdesc[(size_t)i].c_str();
+    return n;
+}
+
+int rdmi_debug_packed(rdmi_ctx* c, const char* key, float* dst, size_t numel, void* stream) {
+    if (!c || !key || !dst) return fail("null argument");
+    auto it = c->wmap.find(key);
+    if (it == c->wmap.end()) return fail("no packed tensor '%s'", key);
+    if (it->second + numel > c->w_floats) return fail("packed tensor '%s': %zu floats exceed the arena", key, numel);
+    HIP_OK(hipMemcpyAsync(dst, c->d_w.get() + it->second, numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
 }
 
 const char* rdmi_path_info(rdmi_ctx* c) {

@@ -111,6 +111,9 @@ struct FOp {
     float* stash;                                 // CONV: global [n][rows][Cout] copy of the finished output (bias, temb, residual, scale applied; before a fused GroupNorm)
     int stash_bf16;                               //   stored as bf16 (train_dtype = bf16)
     int drop_op;                                  // CONV with a fused GroupNorm: >= 0: Dropout_0 on the activated output, mask keyed by (step seed, this layer-plan op index, element)
+    // ---- folded upsample conv (inference programs): every 16-row tile is one output phase of a nearest-x2 upsample + 3x3 conv and contracts
+    //      with ITS OWN ntap = 4 pre-summed weight blocks
+    int w_tile_stride;                            // CONV: bytes between the weight blocks of consecutive row tiles (0: all row tiles share main_ph.w)
 };
 
 struct UnetArgs {
@@ -504,12 +507,12 @@ __device__ __forceinline__ void fconv_main(const OpW& w, const UnetArgs& u, int 
 // PF: steps per straight-line group = depth of the weight ring (4, or 8 where a wave has a single row tile: its steps are only four
 // MFMAs long, so four steps of lookahead are ~1 k cycles -- no more than an L2 round trip under load); the chunk count per tap must be a multiple of PF.
 template <bool DIAG, int NMT, bool LM4 = false, int PF = 4, bool M4 = false>
-__device__ __forceinline__ void fconv_main_t(const OpW& w, const UnetArgs& u, int mt0, int WM, int nt, int lane, long long* fine, f32x4 (&acc)[4]) {
+__device__ __forceinline__ void fconv_main_t(const OpW& w, const UnetArgs& u, int mt0, int WM, int nt, int lane, long long* fine, f32x4 (&acc)[4], unsigned w_off = 0) {
     const int lrow = lane & 15, kq = lane >> 4;
     if (DIAG && fine) fine[0] = clock64();
     const int o_Cout_pad = OPI(w, Cout_pad), o_ntap = OPI(w, ntap);
     const int m_lds = OPI(w, main_ph.lds_off), m_rs = OPI(w, main_ph.rs), nch = OPI(w, main_ph.nch);
-    const WBuf wb = wbuf_make(OPP(w, const float, main_ph.w));
+    const WBuf wb = wbuf_make(reinterpret_cast<const float*>(reinterpret_cast<const char*>(OPP(w, const float, main_ph.w)) + w_off));      // w_off: bytes, wave-uniform (FOp::w_tile_stride)
     const int tab_word = (int)(offsetof(FOp, tab_off) / 4);
     const int zero_off = u.zero_off;
     f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
@@ -999,6 +1002,7 @@ __device__ __forceinline__ void fop_conv(const OpW& w, const UnetArgs& u, int n0
     const float* o_bias = OPP(w, const float, bias); const float* o_bias2 = OPP(w, const float, bias2);
     if (OPI(w, dst_kind) == 3 && OPI(w, qkv1)) { fconv_qkv(w, u, wave, lane); return; }
     const bool fused_gn = OPI(w, dst_kind) == 0 && OPI(w, gn_off) >= 0;      // host guarantees: then every wave has at most one pass below
+    const int wts = OPI(w, w_tile_stride);             // host guarantees: only on ops whose single-tile passes take the tap-major PF = 8 loop
     const int o_samp = MS ? OPI(w, samp) : 0, hw_shift = MS ? OPI(w, hw_shift) : 0;
     const float* dense_base = u.dense + (size_t)max(o_dense, 0);
     f32x4 acc[4];
@@ -1013,9 +1017,11 @@ __device__ __forceinline__ void fop_conv(const OpW& w, const UnetArgs& u, int n0
         const int col = nt * 16 + (lane & 15), colc = min(col, o_Cout - 1);
         float add1 = ldg1(o_bias + colc), add2 = ldg1((o_bias2 ? o_bias2 : o_bias) + colc);
         // this wave's row tiles wm, wm+WM, ... in groups of at most 4 (only NMT 1..4 are instantiated)
-        for (int mt0 = wm; mt0 < mtiles; mt0 += 4 * WM) {
+        // (w_tile_stride != 0, the folded upsample conv: every row tile has its own weights, so no B fragment is shared between row
+        // tiles -- the wave's tiles run one by one through the single-tile loop, each with its own epilogue pass)
+        for (int mt0 = wm; mt0 < mtiles; mt0 += wts ? WM : 4 * WM) {
             const int left = (mtiles - mt0 + WM - 1) >> lWM;
-            const int nmt = left >= 4 ? 4 : left;
+            const int nmt = wts ? 1 : (left >= 4 ? 4 : left);
             // Dense_0(SiLU(temb)) of the sample each row tile belongs to (this lane's rows kq*4..+3 of a tile are one sample)
             float daddm[4] = {0.f, 0.f, 0.f, 0.f};
             float dv = ldg1(dense_base + (o_dense >= 0 ? (size_t)min(n0 + max(o_samp, 0), u.NB - 1) * u.dense_stride + colc : 0));
@@ -1034,7 +1040,7 @@ __device__ __forceinline__ void fop_conv(const OpW& w, const UnetArgs& u, int n0
                     if (OPI(w, rows) <= 4 && OPI(w, dst_kind) != 1 && OPI(w, dst_kind) != 3) {
                         if (tapm8) fconv_main_t<DIAG, 1, false, 8, true>(w, u, mt0, WM, nt, lane, fine, acc);
                         else fconv_main<DIAG, 1, UW_PF_M4, true>(w, u, mt0, WM, nt, lane, fine, acc);
-                    } else if (tapm8) fconv_main_t<DIAG, 1, false, 8>(w, u, mt0, WM, nt, lane, fine, acc);
+                    } else if (tapm8) fconv_main_t<DIAG, 1, false, 8>(w, u, mt0, WM, nt, lane, fine, acc, (unsigned)mt0 * (unsigned)wts);
                     else if (tapm) fconv_main_t<DIAG, 1>(w, u, mt0, WM, nt, lane, fine, acc);
                     else fconv_main<DIAG, 1, UW_PF_N1>(w, u, mt0, WM, nt, lane, fine, acc);
                     break;

@@ -88,6 +88,8 @@ _PROTOS = {
     'rdmi_path_info': ([C.c_void_p], C.c_char_p),
     'rdmi_debug_op_cycles': ([C.c_void_p, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_char_p), C.c_int], C.c_int),
     'rdmi_coop_status': ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
+    'rdmi_debug_program': ([C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.c_int], C.c_int),
+    'rdmi_debug_packed': ([C.c_void_p, C.c_char_p, _F, C.c_size_t, C.c_void_p], C.c_int),
     'rdmi_philox_normal': ([_F, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint, C.c_void_p], C.c_int),
     'rdmi_last_error': ([], C.c_char_p),
     'rdmi_version': ([], C.c_char_p),
@@ -273,6 +275,24 @@ class Context:
 
     def path_info(self):
         return lib().rdmi_path_info(self._h).decode()
+
+    def programs(self):
+        """The fused programs of this context: [dict(S, coop, train, ops=[description per op])] in build order."""
+        out = []
+        while True:
+            S, coop, train = C.c_int(), C.c_int(), C.c_int()
+            desc = (C.c_char_p * 512)()
+            n = lib().rdmi_debug_program(self._h, len(out), C.byref(S), C.byref(coop), C.byref(train), desc, 512)
+            if n < 0:
+                return out
+            out.append(dict(S=S.value, coop=bool(coop.value), train=bool(train.value), ops=[desc[i].decode() for i in range(min(n, 512))]))
+
+    def packed(self, key, numel):
+        """`numel` floats of the packed-weight arena from packed tensor `key` on (after a repack or forward)."""
+        buf = torch.empty(int(numel), dtype=torch.float32, device=self.device)
+        with self._guard():
+            check(lib().rdmi_debug_packed(self._h, key.encode(), ptr(buf), buf.numel(), stream_of(buf)))
+        return buf
 
     def coop_gave_up(self):
         """True if a co-operative launch of this context ever gave up an inter-workgroup wait (synchronises the device)."""
