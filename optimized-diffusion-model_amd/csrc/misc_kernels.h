@@ -21,7 +21,9 @@ struct PackJob {
                               // 3: pack the PRODUCT src (W [Cin][Cout], NIN layout) x src2 (W [Cout][Cout]), 4: the vector src (Cout floats) x src2 -> dst + n_off,
                               // 5: a 3x3 conv that follows a nearest x2 upsample as four 2x2 convs on the source grid: ntap = 16 blocks [phase 2py+px][tap 2ty+tx],
                               //    each the sum of the 3x3 taps that read that source pixel (rdmi.hip: FusedBuilder::conv_up4)
-    const float* src2;        // kinds 3 / 4: the right-hand factor (a NIN weight [in][out])
+                              // 6: pack the PRODUCT src (W [Cin][Cout]) x src2^T (src2 = W2 [Cin][Cout]): M[ci][co] = sum_k W[ci][k] W2[co][k],
+                              // 7: the vector src (Cout floats) x src2^T -> dst + n_off (rdmi.hip: the attention k projection folded into q)
+    const float* src2;        // kinds 3 / 4 / 6 / 7: the right-hand factor (a NIN weight [in][out])
     int col_il;               // kind 2, tiled plan: 0 / 1 none; F = 2 / 4: destination columns are interleaved within groups of 16 F -- column g sits at
                               // position (g / 16F) * 16F + (g % F) * 16 + (g % 16F) / F, so that lane l of the F adjacent 16-column MFMA tiles of a
                               // group holds the F ADJACENT output columns 16F * group + F l .. + F - 1 (tconv_epilogue's vector stores)
@@ -38,6 +40,14 @@ __global__ __launch_bounds__(RDMI_THREADS) void pack_kernel(const PackJob* __res
         for (int i = blockIdx.x * RDMI_THREADS + threadIdx.x; i < j.Cout; i += stride) {
             float acc = 0.f;
             for (int k = 0; k < j.Cin; ++k) acc = fmaf(j.src[k], j.src2[(long)k * j.Cout + i], acc);
+            j.dst[j.n_off + i] = acc;
+        }
+        return;
+    }
+    if (j.kind == 7) {        // row vector x transposed matrix, k ascending: c = bq Wk^T
+        for (int i = blockIdx.x * RDMI_THREADS + threadIdx.x; i < j.Cin; i += stride) {
+            float acc = 0.f;
+            for (int k = 0; k < j.Cout; ++k) acc = fmaf(j.src[k], j.src2[(long)i * j.Cout + k], acc);
             j.dst[j.n_off + i] = acc;
         }
         return;
@@ -75,6 +85,8 @@ __global__ __launch_bounds__(RDMI_THREADS) void pack_kernel(const PackJob* __res
         if (co < j.Cout && ci < j.Cin) {
             if (j.kind == 3) {                            // (W W2)[ci][co]; the middle dimension is W's output = W2's input = Cout channels
                 for (int k = 0; k < j.Cout; ++k) v = fmaf(j.src[(long)ci * j.s_ci + k * j.s_co], j.src2[(long)k * j.Cout + co], v);
+            } else if (j.kind == 6) {                     // (W W2^T)[ci][co], k ascending over the shared OUTPUT channels of W and W2 (square: Cin == Cout)
+                for (int k = 0; k < j.Cout; ++k) v = fmaf(j.src[(long)ci * j.s_ci + k * j.s_co], j.src2[(long)co * j.Cout + k], v);
             } else if (j.kind == 5) {                     // t = 4 * phase + tap of the folded upsample conv: the 3x3 taps that read this phase's source pixel, summed
                 const int py = t >> 3, px = (t >> 2) & 1, ty = (t >> 1) & 1, tx = t & 1;
                 const int ky0 = ty * (1 + py), ky1 = ky0 + 1 + (py != ty);      // py 0: {0}, {1, 2};  py 1: {0, 1}, {2}

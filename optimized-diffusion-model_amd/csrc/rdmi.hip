@@ -356,6 +356,15 @@ inline bool up_fold_shape_ok(int Hs, int Ws, int Cin, int Cout) {
     return std::getenv("RDMI_NO_UP_FOLD") == nullptr && Hs * Ws == 16 && Cin == Cout && Cin % 128 == 0;
 }
 
+// Attention blocks whose k projection is folded into q in the inference programs (fused_attn): the softmax over keys only sees
+// (x M + c) . x^T with M = Wq Wk^T, c = bq Wk^T -- the score terms that depend on the query row alone cancel -- so K is the
+// GroupNorm_0 output x itself and the projection op computes q' and the NIN_3-folded v' only.  The fold rides on the NIN_3 fold and on
+// the single-pass projection (fconv_qkv: C = 64, at most 96 rows).  RDMI_NO_K_FOLD=1 keeps three projections.
+// Asked by the layer plan (does the folded packing exist?) and by the program builder: one rule for both.
+inline bool k_fold_shape_ok(int C, int L) {
+    return std::getenv("RDMI_NO_K_FOLD") == nullptr && std::getenv("RDMI_NO_ATTN_FOLD") == nullptr && std::getenv("RDMI_NO_QKV1") == nullptr && C == 64 && L <= 96;
+}
+
 struct Builder {
     rdmi_ctx* c;
     std::vector<int> ints;       // table / map arena (host)
@@ -536,6 +545,28 @@ struct Builder {
             c->job_param.push_back(c->pindex.at(name + ".NIN_2.b"));
             c->job_param2.resize(c->jobs.size(), -1);
             c->job_param2.back() = c->pindex.at(name + ".NIN_3.W");
+        }
+        if (k_fold_shape_ok(C, a.L)) {   // q' | v' side by side as [C/16][2C][16]: q' = NIN_0.W x NIN_1.W^T with bias NIN_0.b x NIN_1.W^T (the k projection folded
+            // into q, see k_fold_shape_ok), v' as in ".qkv3f".  Products formed on the device at every repack, k ascending.
+            const size_t o2 = alloc_w((size_t)2 * C * C), ob = alloc_w((size_t)2 * C);
+            c->wmap[name + ".qv2f"] = o2;
+            c->wmap[name + ".bqvf"] = ob;
+            for (int i = 0; i < 2; ++i) {
+                PackJob j{};
+                j.dst = reinterpret_cast<float*>(o2);
+                j.Cin = C; j.Cout = C; j.Kpad = C; j.Npad = 2 * C; j.n_off = i * C; j.ntap = 1; j.s_co = 1; j.s_ci = C; j.s_t = 0; j.kind = i == 0 ? 6 : 3;
+                c->jobs.push_back(j);
+                c->job_param.push_back(c->pindex.at(name + (i == 0 ? ".NIN_0.W" : ".NIN_2.W")));
+                c->job_param2.resize(c->jobs.size(), -1);
+                c->job_param2.back() = c->pindex.at(name + (i == 0 ? ".NIN_1.W" : ".NIN_3.W"));
+                PackJob v{};
+                v.dst = reinterpret_cast<float*>(ob);
+                v.Cin = C; v.Cout = C; v.n_off = i * C; v.kind = i == 0 ? 7 : 4;
+                c->jobs.push_back(v);
+                c->job_param.push_back(c->pindex.at(name + (i == 0 ? ".NIN_0.b" : ".NIN_2.b")));
+                c->job_param2.resize(c->jobs.size(), -1);
+                c->job_param2.back() = c->pindex.at(name + (i == 0 ? ".NIN_1.W" : ".NIN_3.W"));
+            }
         }
         op.bqkv_off = alloc_w((size_t)3 * C);
         c->wmap[name + ".bqkv"] = op.bqkv_off;
@@ -1532,35 +1563,45 @@ FusedBuilder::LT fused_attn(FusedBuilder& b, const std::string& name, FusedBuild
     if (b.cur_samp < 0) { b.fail_("attention inside the multi-sample (low-resolution) section is not built"); return x; }
     LT xn = b.talloc(C, H, W);
     b.gn(xn, name + ".GroupNorm_0", false, &x);
-    LT q = b.talloc(C, H, W), k = b.talloc(C, H, W);
-    const int ps = Lpad + 4;
-    const int vt_bytes = C * ps * 4, p_bytes = L * ps * 4;
-    const int vt_off = b.alloc_top(vt_bytes);
     // Inference programs fold NIN_3 into the value projection (weights packed as ".qkv3f" / ".bqkvf"): the attention op then writes
     // (P V' + b3 + x) / sqrt2 itself and the 1x1 NIN_3 conv -- 10-15 k cycles of almost pure per-op overhead, five times per forward --
     // disappears.  The training forward keeps the reference's op sequence (the backward needs the tensor between P V and NIN_3).
     const bool fold3 = !b.train && std::getenv("RDMI_NO_ATTN_FOLD") == nullptr;
-    const size_t bq = c->wmap.at(name + (fold3 ? ".bqkvf" : ".bqkv"));
+    // ... and the k projection into q (k_fold_shape_ok; ".qv2f" / ".bqvf"): no k tensor, the attention op reads xn as K, so xn lives
+    // until after that op, in place of the k tensor of the same size.  (fop_attn clamps key rows to L - 1: nothing is asked of xn's rows beyond L.)
+    const bool foldk = fold3 && k_fold_shape_ok(C, L) && c->wmap.count(name + ".qv2f") != 0;
+    const int NP = foldk ? 2 : 3;
+    LT q = b.talloc(C, H, W), k = foldk ? xn : b.talloc(C, H, W);
+    const int ps = Lpad + 4;
+    const int vt_bytes = C * ps * 4, p_bytes = L * ps * 4;
+    const int vt_off = b.alloc_top(vt_bytes);
+    const size_t bq = c->wmap.at(name + (foldk ? ".bqvf" : fold3 ? ".bqkvf" : ".bqkv"));
     {   // q, k, v in one contraction: the layer plan already packs NIN_0..2 side by side? no: [3][C/16][C][16] -> use the
-        // dedicated fused packing [C/16][3C][16] (wmap key ".qkv3")
-        const int idx = b.conv(xn, H, W, H, W, 1, 0, 1, name + (fold3 ? ".qkv3f" : ".qkv3"), 0, 3 * C, "", bq, 3, &q, 1.f, -1, nullptr, nullptr, "", "");
+        // dedicated fused packing [C/16][3C][16] (wmap key ".qkv3"; [C/16][2C][16] under the k fold)
+        const int idx = b.conv(xn, H, W, H, W, 1, 0, 1, name + (foldk ? ".qv2f" : fold3 ? ".qkv3f" : ".qkv3"), 0, NP * C, "", bq, 3, &q, 1.f, -1, nullptr, nullptr, "", "");
         FOp& o = b.prog.fprog[(size_t)idx];
-        o.dst2_off = k.off; o.dst3_off = vt_off; o.dst3_rs = ps; o.split_C = C;
-        o.qkv1 = (std::getenv("RDMI_NO_QKV1") == nullptr && o.ntap == 1 && o.main_ph.nch == 4 && o.Cout_pad == 192 && C == 64 && o.mtiles <= 6) ? 1 : 0;
+        o.dst2_off = foldk ? q.off : k.off; o.dst3_off = vt_off; o.dst3_rs = ps; o.split_C = C;
+        // the single-pass projection (fconv_qkv): the training kernel holds its three-projection form, the inference kernels the two-projection
+        // form only -- an inference program without the k fold (RDMI_NO_K_FOLD=1, numerical A/B) runs the generic split conv
+        o.qkv1 = (std::getenv("RDMI_NO_QKV1") == nullptr && (b.train || foldk) && o.ntap == 1 && o.main_ph.nch == 4 && o.Cout_pad == NP * 64 && C == 64 && o.mtiles <= 6) ? 1 : 0;
+        if (foldk && !o.qkv1) b.fail_("attention: the k-folded projection needs the single-pass form");
     }
-    b.tfree(xn);
+    if (!foldk) b.tfree(xn);
     const int p_off = b.alloc_top(p_bytes);
-    LT o = b.talloc(C, H, W);
+    // Under the k fold x, xn, q, Vt and P are all live here (xn used to be gone by now): the output goes where q is -- the op reads q
+    // only in its score phase, which a barrier separates from the P V' phase that writes the output.
+    LT o = foldk ? q : b.talloc(C, H, W);
     {
         FOp a = b.blank(FOP_ATTN);
-        a.q_off = q.off; a.k_off = k.off; a.qk_rs = q.rs; a.vt_off = vt_off; a.p_off = p_off; a.ps = ps;
+        a.q_off = q.off; a.k_off = k.off; a.qk_rs = q.rs; a.k_rs = k.rs; a.vt_off = vt_off; a.p_off = p_off; a.ps = ps;
         a.L = L; a.Lpad = Lpad; a.C = C; a.att_scale = 1.0f / std::sqrt((float)C);
         a.dst_off = o.off; a.dst_rs = o.rs;
         if (fold3) { a.resid_off = x.off; a.resid_rs = x.rs; a.scale = (float)(1.0 / std::sqrt(2.0)); }
         const int ia = b.emit(a);
         if (fold3) b.patch_param(ia, FusedBuilder::F_BIAS, name + ".NIN_3.b");
     }
-    b.tfree(q); b.tfree(k);
+    if (!foldk) b.tfree(q);
+    b.tfree(k);                                  // under the k fold: xn
     b.free_bytes(vt_off, vt_bytes); b.free_bytes(p_off, p_bytes);
     if (fold3) { b.tfree(x); return o; }
     LT out = b.talloc(C, H, W);

@@ -97,7 +97,7 @@ struct FOp {
     // (samp < 0: the low-resolution section -- tensors are [S * hw rows][C], row r belongs to sample r >> hw_shift, so every
     // streamed weight fragment feeds S samples).  hw_shift = log2(rows per sample) for multi-sample ops (hw is 4 or 16).
     int samp, hw_shift;
-    int qkv1;                                     // CONV dst_kind 3: run as the single-pass q/k/v projection (fconv_qkv)
+    int qkv1;                                     // CONV dst_kind 3: run as the single-pass q/k/v (training) or q'/v' (inference, Cout = 2C) projection (fconv_qkv)
     // ---- co-operative program (UnetArgs::coop: four workgroups = four CUs share the low-resolution section of their four samples)
     int coop;                                     // CONV: this workgroup computes only ITS quarter of the output columns (member m: column tiles
                                                   // [m * ntiles/4, (m+1) * ntiles/4)) for ALL four samples, K split over the wave groups (fop_conv_coop)
@@ -114,6 +114,8 @@ struct FOp {
     // ---- folded upsample conv (inference programs): every 16-row tile is one output phase of a nearest-x2 upsample + 3x3 conv and contracts
     //      with ITS OWN ntap = 4 pre-summed weight blocks
     int w_tile_stride;                            // CONV: bytes between the weight blocks of consecutive row tiles (0: all row tiles share main_ph.w)
+    // ---- attention with the k projection folded into q (inference programs): K is the GroupNorm_0 output itself
+    int k_rs;                                     // ATTN: row stride of K in floats (qk_rs is Q's)
 };
 
 struct UnetArgs {
@@ -930,7 +932,13 @@ __device__ __forceinline__ void fconv_gn_apply(const OpW& w, const UnetArgs& u, 
 // the generic path gives each wave its three column tiles (the q, k and v tile of its column offset) as three separate passes of
 // four k-steps each -- three prologues and epilogues around 48 MFMAs.  Here the wave loads its 12 weight fragments up front, reads
 // each A fragment once for all three column tiles and runs the 144 MFMAs back to back into 9 accumulator tiles.
-// Preconditions (host: FOp::qkv1 set by the planner): ntap == 1, nch == 4, Cout_pad == 12 tiles (WN = 4, WM = 2), mtiles <= 6.
+// Preconditions (host: FOp::qkv1 set by the planner): ntap == 1, nch == 4, Cout_pad == 4 * NP tiles (WN = 4, WM = 2), mtiles <= 6.
+// NP = 3 (training forward): q -> dst, k -> dst2, v -> dst3 transposed.  NP = 2 (inference programs): the k projection is folded
+// into q (rdmi.hip: fused_attn) -- column tiles 0..3 are q' -> dst, 4..7 are v' -> dst3 transposed, there is no k.
+// There the wave's third row tile (wm + 4) runs in a pass of its own after the first two, and a wave without one (mtiles <= 4 + wm:
+// 72-row images) skips it.  (The one real row of tile 5 at 81 rows on the VALU, as LM4 in fconv_main_t, was measured and is no gain
+// here: DESIGN 4.2g.)
+template <int NP>
 __device__ __forceinline__ void fconv_qkv(const OpW& w, const UnetArgs& u, int wave, int lane) {
     const int lrow = lane & 15, kq = lane >> 4;
     const int wn = wave & 3, wm = wave >> 2;
@@ -942,52 +950,65 @@ __device__ __forceinline__ void fconv_qkv(const OpW& w, const UnetArgs& u, int w
     const int sc_ = OPI(w, split_C), o_dst = OPI(w, dst_off), o_dst2 = OPI(w, dst2_off), o_dst3 = OPI(w, dst3_off), o_dst_rs = OPI(w, dst_rs), rs3 = OPI(w, dst3_rs);
     const short* tab = reinterpret_cast<const short*>(rdmi_lds + opw_at(w, (int)(offsetof(FOp, tab_off) / 4)));
     const size_t bstride = (size_t)o_Cout_pad * 16;
-    f32x4 bf[3][4];
-    float add[3];
+    constexpr int NT1 = NP == 3 ? 3 : 2;                 // row tiles of the first pass (the three-projection form keeps its single pass)
+    f32x4 bf[NP][4];
+    float add[NP];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < NP; ++c) {
         const int col = (wn + 4 * c) * 16 + lrow;
         add[c] = ldg1(o_bias + col);
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) bf[c][ch] = ldg4(m_w + (size_t)col * 16 + kq * 4 + (size_t)ch * bstride);
     }
+    const bool has3 = NP == 3 || wm + 4 < mtiles;        // does this wave own a third row tile?
     int abase[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) abase[i] = arow(tab, min((wm + 2 * i) * 16 + lrow, mtiles * 16 - 1), m_lds, m_rs, u.zero_off) + kq * 16;
-    f32x4 acc[3][3];
+    f32x4 acc[3][NP];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < NP; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch) {
-        f32x4 af[3];
+        f32x4 af[NT1];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) af[i] = *reinterpret_cast<const f32x4*>(rdmi_lds + abase[i] + ch * 64);
+        for (int i = 0; i < NT1; ++i) af[i] = *reinterpret_cast<const f32x4*>(rdmi_lds + abase[i] + ch * 64);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int i = 0; i < 3; ++i)
+            for (int i = 0; i < NT1; ++i)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) acc[i][c] = mfma16(af[i][j], bf[c][ch][j], acc[i][c]);
+                for (int c = 0; c < NP; ++c) acc[i][c] = mfma16(af[i][j], bf[c][ch][j], acc[i][c]);
     }
-    // epilogue: q -> dst, k -> dst2 ([row][col]), v -> dst3 transposed ([col][row], all padded rows written)
+    if (NP == 2 && has3) {
+        f32x4 af[4];
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) af[ch] = *reinterpret_cast<const f32x4*>(rdmi_lds + abase[2] + ch * 64);
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < NP; ++c) acc[2][c] = mfma16(af[ch][j], bf[c][ch][j], acc[2][c]);
+    }
+    // epilogue: q -> dst, k -> dst2 ([row][col]; NP == 3 only), v -> dst3 transposed ([col][row], all padded rows written)
     const int lc = wn * 16 + lrow;                       // column inside q / k / v (split_C = 64 = 4 tiles: tile wn of each)
-    (void)sc_;
+    (void)sc_; (void)o_dst2;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int mt = wm + 2 * i;
         if (mt >= mtiles) continue;
         const int row0 = mt * 16 + kq * 4;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
+        for (int c = 0; c < NP - 1; ++c) {
             float* dstp = lds_f(c == 0 ? o_dst : o_dst2);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (row0 + r < o_rows) dstp[(row0 + r) * o_dst_rs + lc] = (acc[i][c][r] + add[c]) * o_scale;
         }
-        f32x4 v = acc[i][2];
-        for (int r = 0; r < 4; ++r) v[r] = (v[r] + add[2]) * o_scale;
+        f32x4 v = acc[i][NP - 1];
+        for (int r = 0; r < 4; ++r) v[r] = (v[r] + add[NP - 1]) * o_scale;
         *reinterpret_cast<f32x4*>(lds_f(o_dst3) + lc * rs3 + row0) = v;
     }
 }
@@ -1000,7 +1021,7 @@ __device__ __forceinline__ void fop_conv(const OpW& w, const UnetArgs& u, int n0
     const int wn = wave & (WN - 1), wm = wave >> lWN;
     const int o_Cout = OPI(w, Cout), o_dense = OPI(w, dense_off);
     const float* o_bias = OPP(w, const float, bias); const float* o_bias2 = OPP(w, const float, bias2);
-    if (OPI(w, dst_kind) == 3 && OPI(w, qkv1)) { fconv_qkv(w, u, wave, lane); return; }
+    if (OPI(w, dst_kind) == 3 && OPI(w, qkv1)) { fconv_qkv<TR ? 3 : 2>(w, u, wave, lane); return; }      // host: qkv1 only on the form this instantiation holds
     const bool fused_gn = OPI(w, dst_kind) == 0 && OPI(w, gn_off) >= 0;      // host guarantees: then every wave has at most one pass below
     const int wts = OPI(w, w_tile_stride);             // host guarantees: only on ops whose single-tile passes take the tap-major PF = 8 loop
     const int o_samp = MS ? OPI(w, samp) : 0, hw_shift = MS ? OPI(w, hw_shift) : 0;
@@ -1254,19 +1275,19 @@ __device__ __forceinline__ void fop_xchg(const OpW& w, const UnetArgs& u, int g,
 }
 
 // Attention core on LDS tensors: P = softmax(Q K^T * scale) (rows = queries), O = P V.
-// Q, K: [L][qk_rs]; Vt: [C][ps] (keys along the row, all Lpad columns finite); P: [L][ps]; O -> dst [L][dst_rs].
+// Q: [L][qk_rs]; K: [L][k_rs] (rows >= L are never read: with the k projection folded into q, K is the GroupNorm_0 output itself); Vt: [C][ps] (keys along the row, all Lpad columns finite); P: [L][ps]; O -> dst [L][dst_rs].
 // C = 64 channels (one 16-wide channel tile per wave pair).
 __device__ __forceinline__ void fop_attn(const OpW& w, int wave, int lane) {
-    struct { int L, Lpad, q_off, k_off, vt_off, p_off, qk_rs, ps, C, dst_off, dst_rs; float att_scale; } o;
+    struct { int L, Lpad, q_off, k_off, vt_off, p_off, qk_rs, k_rs, ps, C, dst_off, dst_rs; float att_scale; } o;
     o.L = OPI(w, L); o.Lpad = OPI(w, Lpad); o.q_off = OPI(w, q_off); o.k_off = OPI(w, k_off); o.vt_off = OPI(w, vt_off); o.p_off = OPI(w, p_off);
-    o.qk_rs = OPI(w, qk_rs); o.ps = OPI(w, ps); o.C = OPI(w, C); o.dst_off = OPI(w, dst_off); o.dst_rs = OPI(w, dst_rs); o.att_scale = OPF(w, att_scale);
+    o.qk_rs = OPI(w, qk_rs); o.k_rs = OPI(w, k_rs); o.ps = OPI(w, ps); o.C = OPI(w, C); o.dst_off = OPI(w, dst_off); o.dst_rs = OPI(w, dst_rs); o.att_scale = OPF(w, att_scale);
     const int lrow = lane & 15, kq = lane >> 4;
     const int L = o.L, mtiles = o.Lpad >> 4;
     const float* Q = lds_f(o.q_off);
     const float* K = lds_f(o.k_off);
     const float* Vt = lds_f(o.vt_off);
     float* P = lds_f(o.p_off);
-    const int rs = o.qk_rs, ps = o.ps;
+    const int rs = o.qk_rs, krs = o.k_rs, ps = o.ps;
     const int nchq = o.C >> 4;
     // ---- scores + softmax: wave w owns query tile w (tiles >= 8 loop)
     for (int mt = wave; mt < mtiles; mt += UW_WAVES) {
@@ -1280,7 +1301,7 @@ __device__ __forceinline__ void fop_attn(const OpW& w, int wave, int lane) {
             for (int t = 0; t < 6; ++t) {
                 if (t < mtiles) {
                     const int krow = min(t * 16 + lrow, L - 1);
-                    const f32x4 bf = *reinterpret_cast<const f32x4*>(K + (size_t)krow * rs + ch * 16 + kq * 4);
+                    const f32x4 bf = *reinterpret_cast<const f32x4*>(K + (size_t)krow * krs + ch * 16 + kq * 4);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) s[t] = mfma16(af[j], bf[j], s[t]);
                 }
