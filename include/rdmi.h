@@ -240,7 +240,8 @@ int rdmi_set_profiling(rdmi_ctx* ctx, int enabled);
 int rdmi_get_profile(rdmi_ctx* ctx, int index, const char** kernel_name, double* total_ms, long* launches,
                      double* flops_per_launch);
 
-/* Which execution plan the context uses ("fused: ..." or "layers: ... (reason)"). */
+/* Which execution plan the context uses ("fused: ...", "layers: ... (reason)" or "tiled (...): N launches ...; resize launches
+ * (h onto an odd skip grid): R"). */
 const char* rdmi_path_info(rdmi_ctx* ctx);
 
 /* Diagnostic (RDMI_STAMPS=1 at create): shader-clock cycles workgroup 0 spent in each op of the fused program

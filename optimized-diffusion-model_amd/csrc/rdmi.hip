@@ -183,16 +183,18 @@ struct rdmi_ctx {
     // tiled plan (shapes whose samples do not fit one workgroup: csrc/tiled_kernels.h)
     struct TLaunch {
         int kind = 0;                 // 0 conv, 1 GroupNorm statistics (pass over the tensor), 2 batched GEMM, 3 softmax, 4 transpose, 5 statistics from channel sums,
-                                      // 6 GroupNorm(+SiLU) written once as bf16 for a pre-activated conv (bf16 plan), 7 fused softmax(QK^T)V (bf16 plan)
+                                      // 6 GroupNorm(+SiLU) written once as bf16 for a pre-activated conv (bf16 plan), 7 fused softmax(QK^T)V (bf16 plan),
+                                      // 8 nearest resize of h onto the skip tensor's grid (odd level grids)
         std::string name;
+        ResizeArgs rs{};                                                                                        // kind 8 (oA -> oOut)
         TConvArgs conv{}; int nmt = 4; bool pre = false;          // pre: input is the bf16 tensor a kind-6 launch wrote (tconv_pre_kernel)
         size_t oOut2 = (size_t)-1;                                                                              // kind 6: second output (raw bf16 copy)
         GnActArgs gact{}; bool fin = false; size_t oCsA = (size_t)-1, oCsB = (size_t)-1;                        // kind 6 (fin: statistics from the producers' channel records inside the launch)
         FlashArgs flash{}; int flashC = 0;                                                                      // kind 7: fused attention core (bf16 plan)
         const float *sA = nullptr, *sB = nullptr; int CA = 0, CB = 0, HW = 0, G = 0; float* stats = nullptr;     // kind 1
         BgemmArgs gemm{};                                                                                       // kind 2
-        float* sm = nullptr; long rows_per_sample = 0; int L = 0;                                               // kind 3
-        const float* tsrc = nullptr; float* tdst = nullptr; int tL = 0, tC = 0, tld = 0, tc0 = 0; bool t16 = false;   // kind 4 (t16: bf16 elements)
+        float* sm = nullptr; long rows_per_sample = 0; int L = 0, Lp = 0;                                       // kind 3 (Lp: row stride, L rounded up to whole K steps of P V)
+        const float* tsrc = nullptr; float* tdst = nullptr; int tL = 0, tC = 0, tld = 0, tc0 = 0, tLp = 0; bool t16 = false;   // kind 4 (t16: bf16 elements; tLp: row stride of the output)
         int pxA = 0, pxB = 0;                                                                                   // kind 5: pixels per full tile of each producer
         // per-sample workspace offsets (floats) of the operands, resolved to pointers by finish_tiled_plan: NONE = absent, XIN = the NHWC input copy
         static constexpr size_t NONE = (size_t)-1, XIN = (size_t)-2;
@@ -760,15 +762,31 @@ struct TiledBuilder {
         }
         return conv(name + ".Conv_1", h1, nullptr, &st1, name + ".GroupNorm_1", true, 9, 1, false, w1, cout, name + ".Conv_1.bias", (size_t)-1, -1, &A, rs2, false);
     }
+    // h resized onto the skip tensor's grid (RD/models/ncsnpp.py:319-320; an odd level grid: 5x5 -> Downsample -> 2x2 -> Upsample -> 4x4):
+    // the resized NHWC tensor is materialised, so everything downstream reads an ordinary tensor.  It carries no channel records (TT::cs
+    // unset): the producer's records are sums over the SOURCE grid, and the pixel multiplicities differ after the resize, so the
+    // GroupNorm over concat(resized, skip) takes the pass over the tensors (kind 1).
+    TT resize(const std::string& name, const TT& A, int Hd, int Wd) {
+        if (A.bf || A.raw16 || A.C % 4 != 0) throw std::runtime_error("tiled plan: " + name + " needs an fp32 tensor with C % 4 == 0");
+        TT out = talloc(A.C, Hd, Wd);
+        rdmi_ctx::TLaunch l; l.kind = 8; l.name = name; l.oA = A.off; l.oOut = out.off;
+        l.rs.Hs = A.H; l.rs.Ws = A.W; l.rs.Hd = Hd; l.rs.Wd = Wd; l.rs.C = A.C;
+        l.rs.sh = (float)A.H / Hd; l.rs.sw = (float)A.W / Wd;
+        c->tl.push_back(l);
+        return out;
+    }
     // AttnBlockpp (RD/models/layerspp.py:67-96): GN -> q,k,v (one 1x1 conv, Cout = 3C) -> softmax(q k^T / sqrt(C)) v -> NIN_3 -> (x + h)/sqrt2
     TT attn(const std::string& name, const TT& x) {
         const int C = x.C, Lq = x.H * x.W;
-        // C % 32: the q | k | v pack is laid out with K = C unpadded while the 1x1 conv contracts pad32(C) channels.  L = H*W % 16: Q K^T
-        // contracts K = C and P V contracts K = L; bgemm_nt_kernel steps K by 16 and bgemm_nt_bf16_kernel takes any K % 8 == 0 (its last
-        // 32-step is predicated), the row / column tails of both are clamped and masked.  The fused bf16 core has its own rule below
-        // (C of 64 / 128 / 256 and L % 64 == 0) and every other bf16 shape takes the bgemm route.
-        if (C % 32 != 0 || Lq % 16 != 0)
-            throw std::runtime_error(name + ": tiled attention needs C % 32 == 0 and H*W % 16 == 0 (C = " + std::to_string(C) + ", H*W = " + std::to_string(Lq) + ")");
+        // C % 32: the q | k | v pack is laid out with K = C unpadded while the 1x1 conv contracts pad32(C) channels.  Q K^T contracts K = C
+        // and P V contracts K = L: bgemm_nt_kernel steps K by 16 and bgemm_nt_bf16_kernel by 32 (a last step of 16 is predicated), the row /
+        // column tails of both are clamped and masked.  L % 16 != 0 (a 10x10 or 9x9 level): the rows of the score buffer and of V^T are
+        // padded to Lp = L rounded up to 16 (bf16: 32, whole steps) and the pad is written as zeros by the softmax and the transpose, so P V
+        // contracts K = Lp over aligned rows with the same result; L % 16 == 0 keeps Lp = L, the strides and launches it always had.
+        // The fused bf16 core has its own rule below (C of 64 / 128 / 256 and L % 64 == 0) and every other bf16 shape takes the bgemm route.
+        if (C % 32 != 0)
+            throw std::runtime_error(name + ": tiled attention needs C % 32 == 0 (C = " + std::to_string(C) + ", H*W = " + std::to_string(Lq) + ")");
+        const int Lp = Lq % 16 == 0 ? Lq : (bf16() ? (Lq + 31) & ~31 : (Lq + 15) & ~15);
         TT st = stats(name + ".GroupNorm_0", x, nullptr);
         const size_t o3 = b.alloc_w(bf16() ? (size_t)3 * C * C / 2 : (size_t)3 * C * C);
         for (int i = 0; i < 3; ++i) {
@@ -785,33 +803,33 @@ struct TiledBuilder {
         // core's and the transpose's reads; same bits into the MFMAs when 1 / sqrt(C) is a power of two, C = 64 / 256).  RDMI_NO_QKV16=1: fp32
         const bool qkv16 = flash && C % 2 == 0 && std::getenv("RDMI_NO_QKV16") == nullptr;
         TT qkv = conv(name + ".qkv", x, nullptr, &st, name + ".GroupNorm_0", false, 1, 1, false, o3, 3 * C, "", bq, -1, nullptr, 1.f, false, nullptr, qkv16);
-        TT Vt = talloc(qkv16 ? C / 2 : C, Lq, 1);    // [C][L]
+        TT Vt = talloc(qkv16 ? C / 2 : C, Lp, 1);    // [C][Lp]
         TT O = talloc(C, x.H, x.W);
         if (flash) { O.bf = true; }                  // written as bf16 [L][C] (half of the allocation): NIN_3 stages plain copies of it
         if (flash) {
             // bf16 plan: scores, softmax and P V in one kernel (no [L][L] buffer); V^T still comes from the transpose launch
-            { rdmi_ctx::TLaunch l; l.kind = 4; l.name = name + ".vT"; l.oA = qkv.off; l.oOut = Vt.off; l.tL = Lq; l.tC = C; l.tld = 3 * C; l.tc0 = 2 * C; l.t16 = qkv16; c->tl.push_back(l); }
+            { rdmi_ctx::TLaunch l; l.kind = 4; l.name = name + ".vT"; l.oA = qkv.off; l.oOut = Vt.off; l.tL = Lq; l.tC = C; l.tld = 3 * C; l.tc0 = 2 * C; l.tLp = Lq; l.t16 = qkv16; c->tl.push_back(l); }
             rdmi_ctx::TLaunch l; l.kind = 7; l.name = name + ".core"; l.oA = qkv.off; l.oB = Vt.off; l.oOut = O.off;
             l.flash.L = Lq; l.flash.alpha = 1.0f / std::sqrt((float)C); l.flashC = C; l.flash.out_bf16 = 1; l.flash.in_bf16 = qkv16 ? 1 : 0;
             l.flops_per_sample = 4.0 * Lq * Lq * C;
             c->tl.push_back(l);
         } else {
-        TT S = talloc(Lq, Lq, 1);                    // [L][L] scores / probabilities
+        TT S = talloc(Lq, Lp, 1);                    // [L][Lp] scores / probabilities
         {
             rdmi_ctx::TLaunch l; l.kind = 2; l.name = name + ".qk";
             l.oA = qkv.off; l.oB = qkv.off; l.dB = C; l.oC = S.off;
-            l.gemm.sa = l.gemm.sb = (long)Lq * 3 * C; l.gemm.sc = (long)Lq * Lq; l.gemm.lda = l.gemm.ldb = 3 * C; l.gemm.ldc = Lq;
+            l.gemm.sa = l.gemm.sb = (long)Lq * 3 * C; l.gemm.sc = (long)Lq * Lp; l.gemm.lda = l.gemm.ldb = 3 * C; l.gemm.ldc = Lp;
             l.gemm.M = Lq; l.gemm.N = Lq; l.gemm.K = C; l.gemm.alpha = 1.0f / std::sqrt((float)C);
             l.flops_per_sample = 2.0 * Lq * Lq * C;
             c->tl.push_back(l);
         }
-        { rdmi_ctx::TLaunch l; l.kind = 3; l.name = name + ".softmax"; l.oA = S.off; l.rows_per_sample = Lq; l.L = Lq; c->tl.push_back(l); }
-        { rdmi_ctx::TLaunch l; l.kind = 4; l.name = name + ".vT"; l.oA = qkv.off; l.oOut = Vt.off; l.tL = Lq; l.tC = C; l.tld = 3 * C; l.tc0 = 2 * C; c->tl.push_back(l); }
+        { rdmi_ctx::TLaunch l; l.kind = 3; l.name = name + ".softmax"; l.oA = S.off; l.rows_per_sample = Lq; l.L = Lq; l.Lp = Lp; c->tl.push_back(l); }
+        { rdmi_ctx::TLaunch l; l.kind = 4; l.name = name + ".vT"; l.oA = qkv.off; l.oOut = Vt.off; l.tL = Lq; l.tC = C; l.tld = 3 * C; l.tc0 = 2 * C; l.tLp = Lp; c->tl.push_back(l); }
         {
             rdmi_ctx::TLaunch l; l.kind = 2; l.name = name + ".pv";
             l.oA = S.off; l.oB = Vt.off; l.oC = O.off;
-            l.gemm.sa = (long)Lq * Lq; l.gemm.sb = (long)C * Lq; l.gemm.sc = (long)Lq * C; l.gemm.lda = Lq; l.gemm.ldb = Lq; l.gemm.ldc = C;
-            l.gemm.M = Lq; l.gemm.N = C; l.gemm.K = Lq; l.gemm.alpha = 1.f;
+            l.gemm.sa = (long)Lq * Lp; l.gemm.sb = (long)C * Lp; l.gemm.sc = (long)Lq * C; l.gemm.lda = Lp; l.gemm.ldb = Lp; l.gemm.ldc = C;
+            l.gemm.M = Lq; l.gemm.N = C; l.gemm.K = Lp; l.gemm.alpha = 1.f;
             l.flops_per_sample = 2.0 * Lq * Lq * C;
             c->tl.push_back(l);
         }
@@ -855,7 +873,7 @@ int build_tiled_plan(rdmi_ctx* c, Builder& b, const Layout& L, std::map<std::str
             const BlockSpec& bs = L.up[(size_t)u];
             TT sk = hs.back();
             hs.pop_back();
-            if (sk.H != h.H || sk.W != h.W) return fail("tiled plan: skip grid %dx%d != %dx%d (the nearest-resize fix of odd grids is only built for the workgroup-resident plan)", sk.H, sk.W, h.H, h.W);
+            if (sk.H != h.H || sk.W != h.W) h = t.resize("resize." + std::to_string(u), h, sk.H, sk.W);
             h = t.resblock(bs.name, h, &sk, bs.cout, dense_off[bs.name]);
             if (bs.attn) h = t.attn("up_attn." + std::to_string(u), h);
         }
@@ -922,6 +940,8 @@ int finish_tiled_plan(rdmi_ctx* c) {
             l.gact.out = reinterpret_cast<bf16_t*>(tl_ptr(c, l.oOut));
             l.gact.out2 = reinterpret_cast<bf16_t*>(tl_ptr(c, l.oOut2));
             if (l.fin) { l.gact.csA = tl_ptr(c, l.oCsA); l.gact.csB = tl_ptr(c, l.oCsB); l.gact.stats = nullptr; }
+        } else if (l.kind == 8) {
+            l.rs.src = tl_ptr(c, l.oA); l.rs.dst = tl_ptr(c, l.oOut);
         } else {
             l.tsrc = tl_ptr(c, l.oA); l.tdst = tl_ptr(c, l.oOut);
         }
@@ -2304,9 +2324,14 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
         } else if (l.kind == 3) {
             const long rows = l.rows_per_sample * NB;
             ProfScope ps(c, s, "softmax_rows_kernel", 0);
-            hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(RDMI_THREADS), 0, s, l.sm, rows, l.L);
+            hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(RDMI_THREADS), 0, s, l.sm, rows, l.L, l.Lp);
+        } else if (l.kind == 8) {
+            ResizeArgs ra = l.rs; ra.NB = NB;
+            const long n = (long)NB * ra.Hd * ra.Wd * (ra.C / 4);
+            ProfScope ps(c, s, "nearest_resize_kernel", 0);
+            hipLaunchKernelGGL(nearest_resize_kernel, dim3((unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, ra);
         } else {
-            const long n = (long)NB * l.tL * l.tC;
+            const long n = (long)NB * l.tLp * l.tC;
             ProfScope ps(c, s, "transpose_lc_kernel", 0);
             if (l.t16 && l.tL % 64 == 0 && l.tC % 64 == 0)
                 hipLaunchKernelGGL(transpose_lc_tile16_kernel, dim3((unsigned)(l.tL / 64), (unsigned)(l.tC / 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s,
@@ -2315,7 +2340,7 @@ int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_
             else if (l.tL % 64 == 0 && l.tC % 64 == 0)
                 hipLaunchKernelGGL(transpose_lc_tile_kernel, dim3((unsigned)(l.tL / 64), (unsigned)(l.tC / 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, l.tsrc, l.tdst, l.tL, l.tC, l.tld, l.tc0);
             else
-            hipLaunchKernelGGL(transpose_lc_kernel, dim3((unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, l.tsrc, l.tdst, NB, l.tL, l.tC, l.tld, l.tc0);
+            hipLaunchKernelGGL(transpose_lc_kernel, dim3((unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, l.tsrc, l.tdst, NB, l.tL, l.tC, l.tld, l.tc0, l.tLp);
         }
     }
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)c->t_out.get(), out, NB, HW, Cc, 0);
@@ -2397,6 +2422,9 @@ const char* rdmi_path_info(rdmi_ctx* c) {
     if (!c) return "";
     if (c->tiled) {
         s = std::string("tiled (") + (c->arch.compute_dtype == 1 ? "bf16 MFMA operands, fp32 accumulate" : "fp32") + "): " + std::to_string(c->tl.size()) + " launches over HBM-resident NHWC tensors (" + std::to_string(c->t_ws_per_sample * 4 / 1024) + " KiB of activations per sample)";
+        long n_resize = 0;
+        for (auto& l : c->tl) n_resize += l.kind == 8;
+        s += "; resize launches (h onto an odd skip grid): " + std::to_string(n_resize);
     } else if (c->fused_ready() && c->use_fused && !c->debug_taps) {
         s = "fused: workgroup-resident U-Net, " + std::to_string(c->progs[0].fprog.size()) + " ops, " + std::to_string(c->progs[0].fused_lds) + " B LDS";
         for (size_t i = 1; i < c->progs.size(); ++i)

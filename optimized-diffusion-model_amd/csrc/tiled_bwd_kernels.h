@@ -16,9 +16,11 @@
 //   tb_gn_red_kernel       per (sample, group): sum dxhat, sum dxhat * xhat; per (sample, channel): dgamma, dbeta partials
 //   tb_src_grad_kernel     input gradient (GroupNorm backward, or the plain / 2x2-upsample adjoint), added into the sources' twins
 //   tb_softmax_bwd_kernel  dS = P o (dP - rowsum(dP o P)) in place
+//   tb_resize_bwd_kernel   adjoint of the nearest resize of h onto an odd skip grid, added into the source's twin
 #pragma once
 #include "common.h"
 #include "conv_kernel.h"
+#include "tiled_kernels.h"   // ResizeArgs, nearest_src
 
 struct TbGemmArgs {
     int M, N, K;
@@ -303,12 +305,33 @@ __global__ __launch_bounds__(RDMI_THREADS) void tb_rowsum_kernel(const float* __
     out[j] = s;
 }
 
-// dS = P o (dP - sum_j dP o P), one wave per row (in place on dP)
-__global__ __launch_bounds__(RDMI_THREADS) void tb_softmax_bwd_kernel(const float* __restrict__ P, float* dP, long rows, int L) {
+// Adjoint of nearest_resize_kernel: gS[n][sy][sx][c] += sum of gD over the destination pixels that read (sy, sx).  One work-item per
+// SOURCE element: it alone writes that element and adds its destination rows and columns in a fixed order (no atomics: run-to-run
+// identical).  With the rule src = floor(dst * in / out) a source row takes the destination rows of one run (one or two of them
+// when the grid grows by a row, none when it shrinks past it); rows and columns are found independently.
+__global__ __launch_bounds__(RDMI_THREADS) void tb_resize_bwd_kernel(ResizeArgs a, const float* __restrict__ gD, float* gS) {
+    const long i = (long)blockIdx.x * RDMI_THREADS + threadIdx.x;
+    if (i >= (long)a.NB * a.Hs * a.Ws * a.C) return;
+    const int c = (int)(i % a.C);
+    const long r = i / a.C;
+    const int ps = (int)(r % (a.Hs * a.Ws));
+    const long n = r / (a.Hs * a.Ws);
+    const int sy = ps / a.Ws, sx = ps - sy * a.Ws;
+    float g = 0.f;
+    for (int yd = 0; yd < a.Hd; ++yd) {
+        if (nearest_src(yd, a.sh, a.Hs) != sy) continue;
+        for (int xd = 0; xd < a.Wd; ++xd)
+            if (nearest_src(xd, a.sw, a.Ws) == sx) g += gD[((size_t)n * a.Hd * a.Wd + (size_t)yd * a.Wd + xd) * a.C + c];
+    }
+    gS[i] += g;
+}
+
+// dS = P o (dP - sum_j dP o P) over the first L entries of rows of stride ld, one wave per row (in place on dP; a pad [L, ld) is not touched)
+__global__ __launch_bounds__(RDMI_THREADS) void tb_softmax_bwd_kernel(const float* __restrict__ P, float* dP, long rows, int L, int ld) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const float* pr = P + row * L; float* gr = dP + row * L;
+    const float* pr = P + row * ld; float* gr = dP + row * ld;
     float s = 0.f;
     for (int j = lane; j < L; j += 64) s += pr[j] * gr[j];
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);

@@ -13,6 +13,7 @@
 //   gn_stats_kernel  two-pass mean / rstd per (sample, group) over a (possibly concatenated) tensor.
 //   bgemm_nt_kernel  batched C = alpha * A B^T on the fp32 MFMA (attention scores Q K^T and P V with V transposed).
 //   softmax_rows_kernel, transpose_lc_kernel, nchw/nhwc copies: the rest of AttnBlockpp and the API boundary.
+//   nearest_resize_kernel  h resized onto the skip tensor's grid where a level's grid is odd (RD/models/ncsnpp.py:319-320).
 #pragma once
 #include "common.h"
 #include "conv_kernel.h"     // dropout_scale
@@ -919,12 +920,13 @@ __global__ __launch_bounds__(RDMI_THREADS) void bgemm_nt_bf16_kernel(BgemmArgs a
     }
 }
 
-// in-place softmax over the last dimension of [rows][L]: one wave per row (F.softmax(w, dim=-1), layerspp.py:89)
-__global__ __launch_bounds__(RDMI_THREADS) void softmax_rows_kernel(float* __restrict__ x, long rows, int L) {
+// in-place softmax over the first L entries of each row of [rows][ld] (ld >= L: the row stride of a score buffer whose rows are padded
+// to whole K steps of the P V product; the pad [L, ld) is written as zeros): one wave per row (F.softmax(w, dim=-1), layerspp.py:89)
+__global__ __launch_bounds__(RDMI_THREADS) void softmax_rows_kernel(float* __restrict__ x, long rows, int L, int ld) {
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    float* p = x + row * L;
+    float* p = x + row * ld;
     float mx = -3.0e38f;
     for (int i = lane; i < L; i += 64) mx = fmaxf(mx, p[i]);
     for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
@@ -933,6 +935,7 @@ __global__ __launch_bounds__(RDMI_THREADS) void softmax_rows_kernel(float* __res
     for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
     const float inv = 1.0f / s;
     for (int i = lane; i < L; i += 64) p[i] *= inv;
+    for (int i = L + lane; i < ld; i += 64) p[i] = 0.f;
 }
 
 // ---- bf16 plan: softmax(Q K^T / sqrt(C)) V in one kernel (AttnBlockpp, RD/models/layerspp.py:84-92) -----------------------------
@@ -1062,15 +1065,37 @@ __global__ __launch_bounds__(RDMI_THREADS) void flash_attn_bf16_kernel(FlashArgs
     for (int u = 0; u < UT; ++u) *reinterpret_cast<f32x4*>(og + 16 * u + 4 * g) = o[u] * inv;
 }
 
-// dst[n][c][l] = src[n][l][c0 + c] (row stride lds_): V -> V^T for the P V product
-__global__ __launch_bounds__(RDMI_THREADS) void transpose_lc_kernel(const float* __restrict__ src, float* __restrict__ dst, int NB, int L, int C, int ld, int c0) {
+// dst[n][c][l] = src[n][l][c0 + c] (source row stride ld): V -> V^T for the P V product.  The rows of dst hold ldd >= L entries; the pad
+// [L, ldd) is written as zeros (P V contracts whole K steps over it)
+__global__ __launch_bounds__(RDMI_THREADS) void transpose_lc_kernel(const float* __restrict__ src, float* __restrict__ dst, int NB, int L, int C, int ld, int c0, int ldd) {
     const long i = (long)blockIdx.x * RDMI_THREADS + threadIdx.x;
-    if (i >= (long)NB * L * C) return;
-    const int l = (int)(i % L);
-    const long r = i / L;
+    if (i >= (long)NB * ldd * C) return;
+    const int l = (int)(i % ldd);
+    const long r = i / ldd;
     const int c = (int)(r % C);
     const long n = r / C;
-    dst[i] = src[((size_t)n * L + l) * ld + c0 + c];
+    dst[i] = l < L ? src[((size_t)n * L + l) * ld + c0 + c] : 0.f;
+}
+
+// Nearest-neighbour resize of an NHWC tensor onto another grid (NCSNpp.forward resizes h onto the skip tensor's grid when a level's
+// grid is odd: F.interpolate(mode='nearest'), RD/models/ncsnpp.py:319-320): dst[n][yd][xd][:] = src[n][sy(yd)][sx(xd)][:] with
+// sy = min(floor(yd * (Hs / Hd)), Hs - 1) in float, the rule of Builder::nearest_map; H and W are mapped independently.  One work-item
+// per (sample, destination pixel, channel quad): 16-byte loads and stores along C (C % 4 == 0).  sh / sw: Hs / Hd and Ws / Wd as floats,
+// formed on the host.
+struct ResizeArgs { const float* src; float* dst; int Hs, Ws, Hd, Wd, C, NB; float sh, sw; };
+__device__ __forceinline__ int nearest_src(int d, float scale, int n_src) { return min((int)floorf((float)d * scale), n_src - 1); }
+__global__ __launch_bounds__(RDMI_THREADS) void nearest_resize_kernel(ResizeArgs a) {
+    const int C4 = a.C >> 2;
+    const long i = (long)blockIdx.x * RDMI_THREADS + threadIdx.x;
+    if (i >= (long)a.NB * a.Hd * a.Wd * C4) return;
+    const int q = (int)(i % C4);
+    const long r = i / C4;
+    const int pd = (int)(r % (a.Hd * a.Wd));
+    const long n = r / (a.Hd * a.Wd);
+    const int yd = pd / a.Wd, xd = pd - yd * a.Wd;
+    const int sy = nearest_src(yd, a.sh, a.Hs), sx = nearest_src(xd, a.sw, a.Ws);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(a.src + ((size_t)n * a.Hs * a.Ws + (size_t)sy * a.Ws + sx) * a.C + q * 4);
+    *reinterpret_cast<f32x4*>(a.dst + (size_t)i * 4) = v;
 }
 
 // same through a 64 x 64 LDS tile (L, C multiples of 64): both the strided read and the write are 256-byte runs.  grid (L/64, C/64, NB)

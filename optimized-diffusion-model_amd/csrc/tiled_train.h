@@ -215,8 +215,11 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
 // AttnBlockpp core backward on the stored probabilities P (launch `pv`; q | k | v from launch `qk`):
 //   dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dP o P)), dQ = alpha dS K, dK = alpha dS^T Q   (dP / dS live in the twin of S)
 int tiled_attn_backward(rdmi_ctx* c, TiledTrain& tt, const rdmi_ctx::TLaunch& qk, const rdmi_ctx::TLaunch& pv, int NB, hipStream_t s) {
-    const int L = pv.gemm.M, C = pv.gemm.N;
-    const long C3 = 3L * C, LL = (long)L * L, LC3 = L * C3, LC = (long)L * C;
+    // Lp: row stride of P and of its twin (L rounded up to whole K steps of the forward's P V; == L when L % 16 == 0).  Every contraction
+    // here runs over L, and dP / dS are written over [L][L] only: the pad columns of the twin stay at the zeros of the step's memset and
+    // never reach dQ or dK.
+    const int L = pv.gemm.M, C = pv.gemm.N, Lp = pv.gemm.lda;
+    const long C3 = 3L * C, LL = (long)L * Lp, LC3 = L * C3, LC = (long)L * C;
     const float* P = tl_ptr(c, pv.oA);
     const float* qkv = tl_ptr(c, qk.oA);
     float* dS = tl_gptr(c, tt, pv.oA);
@@ -231,14 +234,14 @@ int tiled_attn_backward(rdmi_ctx* c, TiledTrain& tt, const rdmi_ctx::TLaunch& qk
         ProfScope ps(c, s, "tb_gemm_kernel<attn>", 2.0 * M * N * K * NB);
         hipLaunchKernelGGL(tb_gemm_kernel<0>, dim3((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, g);
     };
-    gemm(L, C, L, P, LL, 1, L, dO, LC, C, 1, dqkv + 2 * C, LC3, C3, 1, 1.f);                 // dV[j][c] = sum_i P[i][j] dO[i][c]
-    gemm(L, L, C, dO, LC, C, 1, qkv + 2 * C, LC3, 1, C3, dS, LL, L, 1, 1.f);                 // dP[i][j] = sum_c dO[i][c] V[j][c]
+    gemm(L, C, L, P, LL, 1, Lp, dO, LC, C, 1, dqkv + 2 * C, LC3, C3, 1, 1.f);                // dV[j][c] = sum_i P[i][j] dO[i][c]
+    gemm(L, L, C, dO, LC, C, 1, qkv + 2 * C, LC3, 1, C3, dS, LL, Lp, 1, 1.f);                // dP[i][j] = sum_c dO[i][c] V[j][c]
     {
         ProfScope ps(c, s, "tb_softmax_bwd_kernel", 0);
-        hipLaunchKernelGGL(tb_softmax_bwd_kernel, dim3((unsigned)ceil_div(NB * L, 4)), dim3(RDMI_THREADS), 0, s, P, dS, (long)NB * L, L);
+        hipLaunchKernelGGL(tb_softmax_bwd_kernel, dim3((unsigned)ceil_div(NB * L, 4)), dim3(RDMI_THREADS), 0, s, P, dS, (long)NB * L, L, Lp);
     }
-    gemm(L, C, L, dS, LL, L, 1, qkv + C, LC3, C3, 1, dqkv, LC3, C3, 1, alpha);              // dQ[i][c] = alpha sum_j dS[i][j] K[j][c]
-    gemm(L, C, L, dS, LL, 1, L, qkv, LC3, C3, 1, dqkv + C, LC3, C3, 1, alpha);              // dK[j][c] = alpha sum_i dS[i][j] Q[i][c]
+    gemm(L, C, L, dS, LL, Lp, 1, qkv + C, LC3, C3, 1, dqkv, LC3, C3, 1, alpha);             // dQ[i][c] = alpha sum_j dS[i][j] K[j][c]
+    gemm(L, C, L, dS, LL, 1, Lp, qkv, LC3, C3, 1, dqkv + C, LC3, C3, 1, alpha);             // dK[j][c] = alpha sum_i dS[i][j] Q[i][c]
     return 0;
 }
 
@@ -265,6 +268,11 @@ int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grad
             while (qi >= 0 && c->tl[(size_t)qi].name != qk_name) --qi;
             if (qi < 0) return fail("tiled training: no launch %s", qk_name.c_str());
             if (int e = tiled_attn_backward(c, tt, c->tl[(size_t)qi], l, NB, s)) return e;
+        } else if (l.kind == 8) {   // nearest resize of h onto the skip grid: its twin is complete here (every reader comes later in the list)
+            ResizeArgs ra = l.rs; ra.NB = NB;
+            ProfScope ps(c, s, "tb_resize_bwd_kernel", 0);
+            hipLaunchKernelGGL(tb_resize_bwd_kernel, dim3(tb_blocks((long)NB * ra.Hs * ra.Ws * ra.C)), dim3(RDMI_THREADS), 0, s, ra, (const float*)tl_gptr(c, tt, l.oOut),
+                               tl_gptr(c, tt, l.oA));
         }
         // kinds 1 / 5 (GroupNorm statistics): their gradient is part of the GroupNorm backward; 3 / 4 and `qk`: inside the attention backward
         HIP_OK(hipGetLastError());
