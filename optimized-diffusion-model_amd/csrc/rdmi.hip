@@ -138,6 +138,7 @@ struct Op {
 
 struct ProfEntry { std::string name; double ms = 0; long launches = 0; double flops = 0; };
 struct TrainPlan;                        // csrc/train_plan.h
+struct TiledPlan;                        // csrc/tiled_plan.h
 
 }  // namespace
 
@@ -180,38 +181,9 @@ struct rdmi_ctx {
         bool coop = false; int n_xchg = 0; dev_ptr<unsigned long long> d_xbuf; dev_ptr<int> d_coop_err; int max_nb = 0;     // co-operative program
         bool train = false;                  // the training forward's program (stashes every layer output, applies Dropout_0): never picked for inference
     };
-    // tiled plan (shapes whose samples do not fit one workgroup: csrc/tiled_kernels.h)
-    struct TLaunch {
-        int kind = 0;                 // 0 conv, 1 GroupNorm statistics (pass over the tensor), 2 batched GEMM, 3 softmax, 4 transpose, 5 statistics from channel sums,
-                                      // 6 GroupNorm(+SiLU) written once as bf16 for a pre-activated conv (bf16 plan), 7 fused softmax(QK^T)V (bf16 plan),
-                                      // 8 nearest resize of h onto the skip tensor's grid (odd level grids)
-        std::string name;
-        ResizeArgs rs{};                                                                                        // kind 8 (oA -> oOut)
-        TConvArgs conv{}; int nmt = 4; bool pre = false;          // pre: input is the bf16 tensor a kind-6 launch wrote (tconv_pre_kernel)
-        size_t oOut2 = (size_t)-1;                                                                              // kind 6: second output (raw bf16 copy)
-        GnActArgs gact{}; bool fin = false; size_t oCsA = (size_t)-1, oCsB = (size_t)-1;                        // kind 6 (fin: statistics from the producers' channel records inside the launch)
-        FlashArgs flash{}; int flashC = 0;                                                                      // kind 7: fused attention core (bf16 plan)
-        const float *sA = nullptr, *sB = nullptr; int CA = 0, CB = 0, HW = 0, G = 0; float* stats = nullptr;     // kind 1
-        BgemmArgs gemm{};                                                                                       // kind 2
-        float* sm = nullptr; long rows_per_sample = 0; int L = 0, Lp = 0;                                       // kind 3 (Lp: row stride, L rounded up to whole K steps of P V)
-        const float* tsrc = nullptr; float* tdst = nullptr; int tL = 0, tC = 0, tld = 0, tc0 = 0, tLp = 0; bool t16 = false;   // kind 4 (t16: bf16 elements; tLp: row stride of the output)
-        int pxA = 0, pxB = 0;                                                                                   // kind 5: pixels per full tile of each producer
-        // per-sample workspace offsets (floats) of the operands, resolved to pointers by finish_tiled_plan: NONE = absent, XIN = the NHWC input copy
-        static constexpr size_t NONE = (size_t)-1, XIN = (size_t)-2;
-        size_t oA = NONE, oB = NONE, oStats = NONE, oResid = NONE, oOut = NONE, oC = NONE; long dA = 0, dB = 0;   // dA/dB: interior deltas of GEMM operands
-        bool use_dense = false;
-        std::string p_gamma, p_beta, p_bias; size_t w_off = 0; size_t bias_arena = (size_t)-1;
-        bool in_is_x = false, out_is_final = false;
-        double flops_per_sample = 0;
-    };
-    bool tiled = false;
+    std::unique_ptr<TiledPlan> tiled;    // non-null: the context runs the tiled plan (shapes whose samples do not fit one workgroup: csrc/tiled_plan.h)
     bool in_train_forward = false;       // set around run_forward by rdmi_train_forward
     dev_ptr<bf16_t> d_w16;               // bf16 copies of the forward conv weights (training with compute_dtype = bf16)
-    std::vector<TLaunch> tl;
-    dev_ptr<float> t_ws, t_xin, t_out; size_t t_ws_per_sample = 0;
-    long tiled_min_wgs = 512;                           // a tiled conv widens its workgroups (NCT column tiles per wave) while the launch keeps this many (RDMI_TILED_MIN_WGS: tests)
-    long iconv_min_wgs = LONG_MAX;                      // iconv_kernel from this many 128 x 128 tiles per launch (off unless RDMI_ICONV=1 / RDMI_ICONV_MIN_WGS)
-    dev_ptr<unsigned char> t_zero;                      // 256 zero bytes: iconv_kernel's source for window pixels outside the image
     std::vector<FusedProg> progs;
     int s_min_wg = 256;                            // a program with S samples per workgroup is used from batch s_min_wg * S (RDMI_S_MIN_WG: tests)
     bool use_coop = true;                          // RDMI_COOP=0: never select the co-operative program (A/B, tests)
@@ -242,7 +214,7 @@ struct rdmi_ctx {
     std::vector<int> ev_entry;
     size_t ev_used = 0;
     std::unique_ptr<TrainPlan> train;    // rdmi_enable_training (csrc/train_plan.h)
-    ~rdmi_ctx();                         // defined after train_plan.h: TrainPlan is complete there
+    ~rdmi_ctx();                         // defined after train_plan.h: TiledPlan and TrainPlan are complete there
 };
 
 namespace {
@@ -613,345 +585,10 @@ int add_resblock(Builder& b, const std::string& name, int tA, int tB, int CA, in
 }
 
 
-// ------------------------------------------------------------------------------------------
-// tiled plan (csrc/tiled_kernels.h): NCSNpp.forward (RD/models/ncsnpp.py:226-354) as a list of launches over
-// HBM-resident NHWC tensors, for shapes beyond one workgroup per sample (the CIFAR-shape model of BASELINE config #5)
-// ------------------------------------------------------------------------------------------
-struct TiledBuilder {
-    rdmi_ctx* c; Builder& b;
-    size_t top = 0;                                   // floats per sample allocated so far
-    struct TT { size_t off = 0; int C = 0, H = 0, W = 0; bool valid = false; size_t cs = (size_t)-1; int tiles = 0, tile_px = 0; bool bf = false; bool raw16 = false; };   // raw16: q | k | v stored as bf16 [HW][3C]: only the fused attention core and its V transpose read it   // cs: per-tile channel sums of the producer; bf: a bf16 [HW][C] tensor (C % 64 == 0) for tconv_pre
-    TT talloc(int C, int H, int W) { TT t; t.off = top; t.C = C; t.H = H; t.W = W; t.valid = true; top += ((size_t)C * H * W + 63) & ~(size_t)63; return t; }
-    static int pad32(int a) { return (a + 31) & ~31; }
-
-    bool bf16() const { return c->arch.compute_dtype == 1; }
-    // weights: fp32 [tap][K/16][Np][16], or the bf16 copy [tap][K/32][Np][32] (half the arena floats)
-    size_t pack3x3(const std::string& pre, int cin, int cout) {
-        const int Kp = pad32(cin), Np = pad16(cout);
-        const size_t o = b.alloc_w(bf16() ? ((size_t)9 * Kp * Np + 1) / 2 : (size_t)9 * Kp * Np);
-        b.job_pack(pre + ".weight", o, cin, cout, Kp, Np, 0, 9, (long)cin * 9, 9, 1);
-        if (bf16()) c->jobs.back().kind = 2;
-        return o;
-    }
-    size_t pack1x1(const std::string& pre, int cin, int cout) {
-        const int Kp = pad32(cin), Np = pad16(cout);
-        const size_t o = b.alloc_w(bf16() ? ((size_t)Kp * Np + 1) / 2 : (size_t)Kp * Np);
-        b.job_pack(pre + ".W", o, cin, cout, Kp, Np, 0, 1, 1, cout, 0);
-        if (bf16()) c->jobs.back().kind = 2;
-        return o;
-    }
-    TT stats(const std::string& name, const TT& A, const TT* B) {
-        const int C = A.C + (B ? B->C : 0), G = std::min(C / 4, 32);
-        TT st = talloc(2 * G, 1, 1);
-        if (A.cs != (size_t)-1 && (!B || B->cs != (size_t)-1) && std::getenv("RDMI_TILED_STATS_PASS") == nullptr) {
-            // statistics from the channel sums the producing convs left behind: no pass over the tensors
-            rdmi_ctx::TLaunch f; f.kind = 5; f.name = name + ".stats";
-            f.oA = A.cs; f.oB = B ? B->cs : rdmi_ctx::TLaunch::NONE; f.CA = A.C; f.CB = B ? B->C : 0; f.HW = A.H * A.W; f.G = G;
-            f.tL = A.tiles; f.tC = B ? B->tiles : 0; f.pxA = A.tile_px; f.pxB = B ? B->tile_px : 0; f.oStats = st.off;
-            c->tl.push_back(f);
-            return st;
-        }
-        rdmi_ctx::TLaunch l; l.kind = 1; l.name = name + ".stats";
-        l.oA = A.off; l.oB = B ? B->off : rdmi_ctx::TLaunch::NONE; l.CA = A.C; l.CB = B ? B->C : 0; l.HW = A.H * A.W; l.G = G;
-        l.oStats = st.off;
-        c->tl.push_back(l);
-        return st;
-    }
-    // conv over concat(A, B) [optionally GroupNorm(+SiLU)'d with `st`], 3x3 (stride 1 pad 1 | stride 2 Downsample | nearest x2 Upsample) or 1x1
-    TT conv(const std::string& name, const TT& A, const TT* B, const TT* st, const std::string& gn, bool act, int ntap, int stride, bool up,
-            size_t w_off, int cout, const std::string& bias_param, size_t bias_arena, int dense_off, const TT* resid, float scale, bool final_out,
-            TT* raw_copy = nullptr, bool out16 = false) {       // out16: the output is stored as bf16 (TT::raw16)     // raw_copy: if the conv takes the pre-activated form, its activation pass also leaves the RAW input as a bf16 [HW][Cv] tensor here
-        // bf16 plan: a 3x3 stride-1 conv behind a GroupNorm reads a tensor that was normalised, activated and rounded to bf16 ONCE
-        // (kind 6) instead of redoing that arithmetic for every staged window element (RDMI_NO_PREACT=1: the one-kernel form)
-        // (3x3 stride-1 convs and the 1x1 q/k/v projection of attention blocks); a tensor that already is bf16 (the fused attention
-        // core's output) goes to the same kernel without the extra pass.
-        const bool direct = A.bf && !B && !st && ntap == 1;
-        const bool pre = direct || (bf16() && st && (ntap == 9 || ntap == 1) && stride == 1 && !up && !final_out && cout % 16 == 0 && A.C % 4 == 0 &&
-                                    (!B || B->C % 4 == 0) && (A.C + (B ? B->C : 0)) % 64 == 0 && std::getenv("RDMI_NO_PREACT") == nullptr);
-        if (A.bf && !direct) throw std::runtime_error("tiled plan: a bf16 tensor feeds a conv that cannot take it (" + name + ")");
-        if (A.raw16 || (B && B->raw16) || (resid && resid->raw16)) throw std::runtime_error("tiled plan: a bf16-stored q | k | v tensor is read by a conv (" + name + ")");
-        size_t act_off = A.off;
-        if (pre && !direct) {
-            const int Cin = A.C + (B ? B->C : 0), Cvp = pad32(Cin);
-            TT actT = talloc((Cvp + 1) / 2, A.H, A.W);               // bf16 [HW][Cv]
-            act_off = actT.off;
-            rdmi_ctx::TLaunch g; g.kind = 6; g.name = name + ".act";
-            g.oA = A.off; g.oB = B ? B->off : rdmi_ctx::TLaunch::NONE; g.oStats = st->off; g.oOut = actT.off;
-            if (raw_copy && std::getenv("RDMI_NO_RAW_COPY") == nullptr) {
-                *raw_copy = talloc((Cvp + 1) / 2, A.H, A.W);
-                raw_copy->C = Cvp; raw_copy->bf = true;
-                g.oOut2 = raw_copy->off;
-            }
-            g.gact.CA = A.C; g.gact.CB = B ? B->C : 0; g.gact.Cv = Cvp; g.gact.HW = A.H * A.W;
-            g.gact.G = std::min(Cin / 4, 32); g.gact.Cg = Cin / g.gact.G; g.gact.act = act ? 1 : 0;
-            g.p_gamma = gn + ".weight"; g.p_beta = gn + ".bias";
-            // the statistics launch of this GroupNorm (kind 5: from the producers' channel records) is folded into the activation pass:
-            // gn_act_fin_kernel reads the records itself (RDMI_NO_GN_FOLD=1 keeps the two launches)
-            int max_slots = 0;                                          // groups a 64-channel slice touches (the kernel's table holds 16)
-            for (int c_lo = 0; c_lo < Cin; c_lo += 64) max_slots = std::max(max_slots, (std::min(c_lo + 64, Cin) - 1) / g.gact.Cg - c_lo / g.gact.Cg + 1);
-            if (Cvp % 64 == 0 && max_slots <= 16 && g.gact.Cg <= 16 && std::getenv("RDMI_NO_GN_FOLD") == nullptr)
-                for (size_t k = c->tl.size(); k-- > 0 && k + 4 > c->tl.size();)
-                    if (c->tl[k].kind == 5 && c->tl[k].oStats == st->off) {
-                        const rdmi_ctx::TLaunch& f = c->tl[k];
-                        g.fin = true; g.oCsA = f.oA; g.oCsB = f.oB;
-                        g.gact.tilesA = f.tL; g.gact.tilesB = f.tC; g.gact.pxA = f.pxA; g.gact.pxB = f.pxB; g.gact.eps = 1e-6f;
-                        c->tl.erase(c->tl.begin() + (long)k);
-                        break;
-                    }
-            c->tl.push_back(g);
-        }
-        TConvArgs a{};
-        a.CA = A.C; a.CB = B ? B->C : 0; a.Cv = pad32(a.CA + a.CB);
-        if (pre) { a.CA = a.Cv; a.CB = 0; }
-        a.Ha = A.H; a.Wa = A.W; a.up = up ? 1 : 0; a.Hv = up ? 2 * A.H : A.H; a.Wv = up ? 2 * A.W : A.W;
-        a.stride = stride; a.ntap = ntap; a.pad_lo = (ntap == 9 && stride == 1) ? 1 : 0;
-        a.Ho = stride == 2 ? (a.Hv + 1 - 3) / 2 + 1 : a.Hv; a.Wo = stride == 2 ? (a.Wv + 1 - 3) / 2 + 1 : a.Wv;
-        a.TR = a.Wo >= 64 ? 1 : std::max(1, std::min(a.Ho, 64 / a.Wo));
-        if (st && !pre) { a.G = std::min((a.CA + a.CB) / 4, 32); a.Cg = (a.CA + a.CB) / a.G; a.act = act ? 1 : 0; }
-        a.dense_off = dense_off < 0 ? 0 : dense_off; a.dense_stride = c->dense_total;
-        a.out_scale = scale;
-        a.Cout = cout; a.Cout_pad = pad16(cout);
-        // bf16 packs: interleave the weights' columns by the NCT the launch will use at the sampling batch (run_tiled's rule at 128 forwards),
-        // so that the epilogue's loads and stores are 8- / 16-byte vectors over full lines (tconv_epilogue; RDMI_NO_COL_IL=1: plain order)
-        if (bf16() && std::getenv("RDMI_NO_COL_IL") == nullptr) {
-            const long tl = ceil_div(a.Ho, a.TR);
-            for (int cand : {4, 2})
-                if (cout % (16 * cand) == 0 && a.Cout_pad >= 64 * cand && tl * 128 * ceil_div(a.Cout_pad, 64 * cand) >= 512) { a.col_il = cand; break; }
-            if (a.col_il > 1)
-                for (auto& j : c->jobs) if (j.kind == 2 && j.dst == reinterpret_cast<float*>(w_off)) j.col_il = a.col_il;
-        }
-        TT out = talloc(out16 ? (cout + 1) / 2 : cout, a.Ho, a.Wo);
-        out.C = cout; out.raw16 = out16; a.out_bf16 = out16 ? 1 : 0;
-        size_t cs_off = rdmi_ctx::TLaunch::NONE;
-        if (!final_out && cout % 4 == 0) {
-            out.tiles = ceil_div(a.Ho, a.TR); out.tile_px = a.TR * a.Wo;
-            TT cs = talloc(2 * cout * out.tiles, 1, 1);
-            out.cs = cs_off = cs.off;
-        }
-        rdmi_ctx::TLaunch l; l.kind = 0; l.name = name; l.conv = a;
-        l.oC = cs_off;
-        l.oA = A.off; l.oB = B ? B->off : rdmi_ctx::TLaunch::NONE; l.oStats = st ? st->off : rdmi_ctx::TLaunch::NONE;
-        if (pre) { l.pre = true; l.oA = act_off; l.oB = rdmi_ctx::TLaunch::NONE; l.oStats = rdmi_ctx::TLaunch::NONE; }
-        l.oResid = resid ? resid->off : rdmi_ctx::TLaunch::NONE; l.oOut = out.off;
-        l.nmt = (a.TR * a.Wo > 16) ? 4 : 1;
-        l.w_off = w_off; l.p_bias = bias_param; l.bias_arena = bias_arena;
-        if (st && !pre) { l.p_gamma = gn + ".weight"; l.p_beta = gn + ".bias"; }
-        l.out_is_final = final_out;
-        l.use_dense = dense_off >= 0;
-        l.flops_per_sample = 2.0 * a.Ho * a.Wo * cout * (double)ntap * (A.C + (B ? B->C : 0));
-        c->tl.push_back(l);
-        return out;
-    }
-    TT resblock(const std::string& name, const TT& A, const TT* B, int cout, int dense_off) {
-        const int cin = A.C + (B ? B->C : 0);
-        const float rs2 = (float)(1.0 / std::sqrt(2.0));
-        TT st0 = stats(name + ".GroupNorm_0", A, B);
-        // bf16 plan: GroupNorm_0's activation pass reads the block's raw input anyway and leaves a bf16 copy of it for the NIN_0
-        // shortcut, which then is a copy-staged 1x1 conv over half the bytes instead of a conv that converts fp32 while staging
-        TT xraw;
-        TT h1 = conv(name + ".Conv_0", A, B, &st0, name + ".GroupNorm_0", true, 9, 1, false, pack3x3(name + ".Conv_0", cin, cout), cout,
-                     name + ".Conv_0.bias", (size_t)-1, dense_off, nullptr, 1.f, false, cin != cout ? &xraw : nullptr);
-        TT st1 = stats(name + ".GroupNorm_1", h1, nullptr);
-        const size_t w1 = pack3x3(name + ".Conv_1", cout, cout);
-        if (cin != cout) {
-            TT sc = xraw.valid ? conv(name + ".NIN_0", xraw, nullptr, nullptr, "", false, 1, 1, false, pack1x1(name + ".NIN_0", cin, cout), cout, name + ".NIN_0.b", (size_t)-1, -1,
-                                      nullptr, 1.f, false)
-                               : conv(name + ".NIN_0", A, B, nullptr, "", false, 1, 1, false, pack1x1(name + ".NIN_0", cin, cout), cout, name + ".NIN_0.b", (size_t)-1, -1,
-                                      nullptr, 1.f, false);
-            return conv(name + ".Conv_1", h1, nullptr, &st1, name + ".GroupNorm_1", true, 9, 1, false, w1, cout, name + ".Conv_1.bias", (size_t)-1, -1, &sc, rs2, false);
-        }
-        return conv(name + ".Conv_1", h1, nullptr, &st1, name + ".GroupNorm_1", true, 9, 1, false, w1, cout, name + ".Conv_1.bias", (size_t)-1, -1, &A, rs2, false);
-    }
-    // h resized onto the skip tensor's grid (RD/models/ncsnpp.py:319-320; an odd level grid: 5x5 -> Downsample -> 2x2 -> Upsample -> 4x4):
-    // the resized NHWC tensor is materialised, so everything downstream reads an ordinary tensor.  It carries no channel records (TT::cs
-    // unset): the producer's records are sums over the SOURCE grid, and the pixel multiplicities differ after the resize, so the
-    // GroupNorm over concat(resized, skip) takes the pass over the tensors (kind 1).
-    TT resize(const std::string& name, const TT& A, int Hd, int Wd) {
-        if (A.bf || A.raw16 || A.C % 4 != 0) throw std::runtime_error("tiled plan: " + name + " needs an fp32 tensor with C % 4 == 0");
-        TT out = talloc(A.C, Hd, Wd);
-        rdmi_ctx::TLaunch l; l.kind = 8; l.name = name; l.oA = A.off; l.oOut = out.off;
-        l.rs.Hs = A.H; l.rs.Ws = A.W; l.rs.Hd = Hd; l.rs.Wd = Wd; l.rs.C = A.C;
-        l.rs.sh = (float)A.H / Hd; l.rs.sw = (float)A.W / Wd;
-        c->tl.push_back(l);
-        return out;
-    }
-    // AttnBlockpp (RD/models/layerspp.py:67-96): GN -> q,k,v (one 1x1 conv, Cout = 3C) -> softmax(q k^T / sqrt(C)) v -> NIN_3 -> (x + h)/sqrt2
-    TT attn(const std::string& name, const TT& x) {
-        const int C = x.C, Lq = x.H * x.W;
-        // C % 32: the q | k | v pack is laid out with K = C unpadded while the 1x1 conv contracts pad32(C) channels.  Q K^T contracts K = C
-        // and P V contracts K = L: bgemm_nt_kernel steps K by 16 and bgemm_nt_bf16_kernel by 32 (a last step of 16 is predicated), the row /
-        // column tails of both are clamped and masked.  L % 16 != 0 (a 10x10 or 9x9 level): the rows of the score buffer and of V^T are
-        // padded to Lp = L rounded up to 16 (bf16: 32, whole steps) and the pad is written as zeros by the softmax and the transpose, so P V
-        // contracts K = Lp over aligned rows with the same result; L % 16 == 0 keeps Lp = L, the strides and launches it always had.
-        // The fused bf16 core has its own rule below (C of 64 / 128 / 256 and L % 64 == 0) and every other bf16 shape takes the bgemm route.
-        if (C % 32 != 0)
-            throw std::runtime_error(name + ": tiled attention needs C % 32 == 0 (C = " + std::to_string(C) + ", H*W = " + std::to_string(Lq) + ")");
-        const int Lp = Lq % 16 == 0 ? Lq : (bf16() ? (Lq + 31) & ~31 : (Lq + 15) & ~15);
-        TT st = stats(name + ".GroupNorm_0", x, nullptr);
-        const size_t o3 = b.alloc_w(bf16() ? (size_t)3 * C * C / 2 : (size_t)3 * C * C);
-        for (int i = 0; i < 3; ++i) {
-            PackJob j{};
-            j.dst = reinterpret_cast<float*>(o3);
-            j.Cin = C; j.Cout = C; j.Kpad = C; j.Npad = 3 * C; j.n_off = i * C; j.ntap = 1; j.s_co = 1; j.s_ci = C; j.s_t = 0; j.kind = bf16() ? 2 : 0;
-            c->jobs.push_back(j);
-            c->job_param.push_back(c->pindex.at(name + ".NIN_" + std::to_string(i) + ".W"));
-        }
-        const size_t bq = b.alloc_w((size_t)3 * C);
-        for (int i = 0; i < 3; ++i) b.job_copy(name + ".NIN_" + std::to_string(i) + ".b", bq, C, i * C);
-        const bool flash = bf16() && (C == 64 || C == 128 || C == 256) && Lq % 64 == 0 && std::getenv("RDMI_NO_FLASH") == nullptr;
-        // the fused core rounds q, k, v to bf16 before its MFMAs anyway: the projection stores them as bf16 (half the conv's writes, half the
-        // core's and the transpose's reads; same bits into the MFMAs when 1 / sqrt(C) is a power of two, C = 64 / 256).  RDMI_NO_QKV16=1: fp32
-        const bool qkv16 = flash && C % 2 == 0 && std::getenv("RDMI_NO_QKV16") == nullptr;
-        TT qkv = conv(name + ".qkv", x, nullptr, &st, name + ".GroupNorm_0", false, 1, 1, false, o3, 3 * C, "", bq, -1, nullptr, 1.f, false, nullptr, qkv16);
-        TT Vt = talloc(qkv16 ? C / 2 : C, Lp, 1);    // [C][Lp]
-        TT O = talloc(C, x.H, x.W);
-        if (flash) { O.bf = true; }                  // written as bf16 [L][C] (half of the allocation): NIN_3 stages plain copies of it
-        if (flash) {
-            // bf16 plan: scores, softmax and P V in one kernel (no [L][L] buffer); V^T still comes from the transpose launch
-            { rdmi_ctx::TLaunch l; l.kind = 4; l.name = name + ".vT"; l.oA = qkv.off; l.oOut = Vt.off; l.tL = Lq; l.tC = C; l.tld = 3 * C; l.tc0 = 2 * C; l.tLp = Lq; l.t16 = qkv16; c->tl.push_back(l); }
-            rdmi_ctx::TLaunch l; l.kind = 7; l.name = name + ".core"; l.oA = qkv.off; l.oB = Vt.off; l.oOut = O.off;
-            l.flash.L = Lq; l.flash.alpha = 1.0f / std::sqrt((float)C); l.flashC = C; l.flash.out_bf16 = 1; l.flash.in_bf16 = qkv16 ? 1 : 0;
-            l.flops_per_sample = 4.0 * Lq * Lq * C;
-            c->tl.push_back(l);
-        } else {
-        TT S = talloc(Lq, Lp, 1);                    // [L][Lp] scores / probabilities
-        {
-            rdmi_ctx::TLaunch l; l.kind = 2; l.name = name + ".qk";
-            l.oA = qkv.off; l.oB = qkv.off; l.dB = C; l.oC = S.off;
-            l.gemm.sa = l.gemm.sb = (long)Lq * 3 * C; l.gemm.sc = (long)Lq * Lp; l.gemm.lda = l.gemm.ldb = 3 * C; l.gemm.ldc = Lp;
-            l.gemm.M = Lq; l.gemm.N = Lq; l.gemm.K = C; l.gemm.alpha = 1.0f / std::sqrt((float)C);
-            l.flops_per_sample = 2.0 * Lq * Lq * C;
-            c->tl.push_back(l);
-        }
-        { rdmi_ctx::TLaunch l; l.kind = 3; l.name = name + ".softmax"; l.oA = S.off; l.rows_per_sample = Lq; l.L = Lq; l.Lp = Lp; c->tl.push_back(l); }
-        { rdmi_ctx::TLaunch l; l.kind = 4; l.name = name + ".vT"; l.oA = qkv.off; l.oOut = Vt.off; l.tL = Lq; l.tC = C; l.tld = 3 * C; l.tc0 = 2 * C; l.tLp = Lp; c->tl.push_back(l); }
-        {
-            rdmi_ctx::TLaunch l; l.kind = 2; l.name = name + ".pv";
-            l.oA = S.off; l.oB = Vt.off; l.oC = O.off;
-            l.gemm.sa = (long)Lq * Lp; l.gemm.sb = (long)C * Lp; l.gemm.sc = (long)Lq * C; l.gemm.lda = Lp; l.gemm.ldb = Lp; l.gemm.ldc = C;
-            l.gemm.M = Lq; l.gemm.N = C; l.gemm.K = Lp; l.gemm.alpha = 1.f;
-            l.flops_per_sample = 2.0 * Lq * Lq * C;
-            c->tl.push_back(l);
-        }
-        }
-        return conv(name + ".NIN_3", O, nullptr, nullptr, "", false, 1, 1, false, pack1x1(name + ".NIN_3", C, C), C, name + ".NIN_3.b", (size_t)-1, -1, &x,
-                    (float)(1.0 / std::sqrt(2.0)), false);
-    }
-};
-
-int build_tiled_plan(rdmi_ctx* c, Builder& b, const Layout& L, std::map<std::string, int>& dense_off) {
-    const rdmi_arch& a = c->arch;
-    using TT = TiledBuilder::TT;
-    TiledBuilder t{c, b};
-    int H = c->H, W = c->W;
-    TT xin = t.talloc(a.channels, H, W);               // NHWC copy of the caller's NCHW input
-    xin.off = rdmi_ctx::TLaunch::XIN;                  // marker: resolved to t_xin
-    TT h = t.conv("input_conv", xin, nullptr, nullptr, "", false, 9, 1, false, t.pack3x3("input_conv", a.channels, a.nf), a.nf, "input_conv.bias", (size_t)-1, -1,
-                  nullptr, 1.f, false);
-    c->tl.back().in_is_x = true;
-    std::vector<TT> hs{h};
-    int d = 0;
-    for (int i = 0; i < a.n_levels; ++i) {
-        for (int j = 0; j < a.num_res_blocks; ++j, ++d) {
-            const BlockSpec& bs = L.down[(size_t)d];
-            h = t.resblock(bs.name, h, nullptr, bs.cout, dense_off[bs.name]);
-            if (bs.attn) h = t.attn("down_attn." + std::to_string(d), h);
-            hs.push_back(h);
-        }
-        hs.push_back(h);
-        if (i != a.n_levels - 1) {
-            const std::string nm = "downsample." + std::to_string(i) + ".Conv_0";
-            h = t.conv(nm, h, nullptr, nullptr, "", false, 9, 2, false, t.pack3x3(nm, h.C, h.C), h.C, nm + ".bias", (size_t)-1, -1, nullptr, 1.f, false);
-        }
-    }
-    h = t.resblock("mid_block1", h, nullptr, L.mid_ch, dense_off["mid_block1"]);
-    if (a.attn_levels >> (a.n_levels - 1) & 1) return fail("attention at the bottleneck resolution (mid_attn) is not built");
-    h = t.resblock("mid_block2", h, nullptr, L.mid_ch, dense_off["mid_block2"]);
-    int u = 0;
-    for (int k = 0; k < a.n_levels; ++k) {
-        for (int j = 0; j < a.num_res_blocks + 1; ++j, ++u) {
-            const BlockSpec& bs = L.up[(size_t)u];
-            TT sk = hs.back();
-            hs.pop_back();
-            if (sk.H != h.H || sk.W != h.W) h = t.resize("resize." + std::to_string(u), h, sk.H, sk.W);
-            h = t.resblock(bs.name, h, &sk, bs.cout, dense_off[bs.name]);
-            if (bs.attn) h = t.attn("up_attn." + std::to_string(u), h);
-        }
-        if (k != a.n_levels - 1) {
-            const std::string nm = "upsample." + std::to_string(k) + ".Conv_0";
-            h = t.conv(nm, h, nullptr, nullptr, "", false, 9, 1, true, t.pack3x3(nm, h.C, h.C), h.C, nm + ".bias", (size_t)-1, -1, nullptr, 1.f, false);
-        }
-    }
-    if (h.H != c->H || h.W != c->W) return fail("network output grid %dx%d != input %dx%d", h.H, h.W, c->H, c->W);
-    TT st = t.stats("out_norm", h, nullptr);
-    t.conv("out_conv", h, nullptr, &st, "out_norm", true, 9, 1, false, t.pack3x3("out_conv", h.C, a.channels), a.channels, "out_conv.bias", (size_t)-1, -1, nullptr, 1.f, true);
-    c->t_ws_per_sample = t.top;
-    c->tiled = true;
-    return 0;
-}
-
-// resolve a per-sample workspace offset to a device pointer (tensors are [tensor][n][...]: the offset scales with max_batch)
-inline float* tl_ptr(rdmi_ctx* c, size_t off, long delta = 0) {
-    if (off == rdmi_ctx::TLaunch::NONE) return nullptr;
-    if (off == rdmi_ctx::TLaunch::XIN) return c->t_xin.get();
-    return c->t_ws.get() + off * (size_t)c->max_batch + delta;
-}
-
-int finish_tiled_plan(rdmi_ctx* c) {
-    const size_t NBmax = (size_t)c->max_batch;
-    const size_t E = (size_t)c->H * c->W * c->arch.channels;
-    HIP_OK(hip_alloc(c->t_ws, c->t_ws_per_sample * NBmax));
-    HIP_OK(hip_alloc(c->t_xin, E * NBmax));
-    HIP_OK(hip_alloc(c->t_out, E * NBmax));
-    HIP_OK(hip_alloc(c->t_zero, 256));
-    HIP_OK(hipMemset(c->t_zero.get(), 0, 256));
-    // measured on MI355X (rocprofv3 kernel trace, B = 64 with guidance): 5.28 ms for the 3x3 convs of the 32x32 / 16x16 levels against 4.88 ms
-    // with tconv_pre_kernel -- the implicit-GEMM form is NOT the default; RDMI_ICONV=1 selects it (from RDMI_ICONV_MIN_WGS tiles, default 256)
-    if (const char* e = std::getenv("RDMI_TILED_MIN_WGS")) c->tiled_min_wgs = std::atol(e);
-    c->iconv_min_wgs = LONG_MAX;
-    if (const char* e = std::getenv("RDMI_ICONV")) if (std::atoi(e) != 0) c->iconv_min_wgs = 256;
-    if (const char* e = std::getenv("RDMI_ICONV_MIN_WGS")) c->iconv_min_wgs = std::atol(e);
-    for (auto& l : c->tl) {
-        if (l.kind == 0) {
-            TConvArgs& a = l.conv;
-            a.srcA = tl_ptr(c, l.oA); a.srcB = tl_ptr(c, l.oB); a.stats = tl_ptr(c, l.oStats); a.resid = tl_ptr(c, l.oResid);
-            a.out = l.out_is_final ? c->t_out.get() : tl_ptr(c, l.oOut);
-            a.wpk = c->d_w.get() + l.w_off;
-            a.dense = l.use_dense ? c->d_dense.get() : nullptr;
-            a.chsum = tl_ptr(c, l.oC);
-            a.zeros = c->t_zero.get();
-            if (l.pre && tconv_trv(a) * tconv_wl(a) * (a.ntap == 1 ? TpCfg<1>::UPP : TpCfg<9>::UPP) > TC_MAXS * RDMI_THREADS)
-                return fail("tiled conv %s: window of %d pixels exceeds the register staging", l.name.c_str(), tconv_trv(a) * tconv_wl(a));
-            if (l.pre && tconv_pre_lds_bytes(a) > 160 * 1024) return fail("tiled conv %s: LDS window %zu B", l.name.c_str(), tconv_pre_lds_bytes(a));
-            if (tconv_lds_bytes(a) > 160 * 1024) return fail("tiled conv %s: LDS window %zu B", l.name.c_str(), tconv_lds_bytes(a));
-            if (tconv_trv(a) * tconv_wl(a) * 8 > TC_MAXS * RDMI_THREADS) return fail("tiled conv %s: window of %d pixels exceeds the register staging (%d float4 per work-item)", l.name.c_str(), tconv_trv(a) * tconv_wl(a), TC_MAXS);
-        } else if (l.kind == 1) {
-            l.sA = tl_ptr(c, l.oA); l.sB = tl_ptr(c, l.oB); l.stats = tl_ptr(c, l.oStats);
-        } else if (l.kind == 2) {
-            l.gemm.A = tl_ptr(c, l.oA, l.dA); l.gemm.B = tl_ptr(c, l.oB, l.dB); l.gemm.C = tl_ptr(c, l.oC);
-        } else if (l.kind == 3) {
-            l.sm = tl_ptr(c, l.oA);
-        } else if (l.kind == 5) {
-            l.sA = tl_ptr(c, l.oA); l.sB = tl_ptr(c, l.oB); l.stats = tl_ptr(c, l.oStats);
-        } else if (l.kind == 7) {
-            l.flash.qkv = tl_ptr(c, l.oA); l.flash.vt = tl_ptr(c, l.oB); l.flash.out = tl_ptr(c, l.oOut);
-        } else if (l.kind == 6) {
-            l.gact.A = tl_ptr(c, l.oA); l.gact.B = tl_ptr(c, l.oB); l.gact.stats = tl_ptr(c, l.oStats);
-            l.gact.out = reinterpret_cast<bf16_t*>(tl_ptr(c, l.oOut));
-            l.gact.out2 = reinterpret_cast<bf16_t*>(tl_ptr(c, l.oOut2));
-            if (l.fin) { l.gact.csA = tl_ptr(c, l.oCsA); l.gact.csB = tl_ptr(c, l.oCsB); l.gact.stats = nullptr; }
-        } else if (l.kind == 8) {
-            l.rs.src = tl_ptr(c, l.oA); l.rs.dst = tl_ptr(c, l.oOut);
-        } else {
-            l.tsrc = tl_ptr(c, l.oA); l.tdst = tl_ptr(c, l.oOut);
-        }
-    }
-    return 0;
-}
-
-// replay the tiled plan for NB samples (embedding already evaluated into d_dense); x is NCHW, out is NCHW
-int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_mod, int sig_is_time, float t_scalar, float smin, float ratio, float* out, int NB,
-              const float* dense_rows, hipStream_t s);
+// the tiled plan (csrc/tiled_plan.h, included ahead of run_forward): shapes beyond one workgroup per sample
+int build_tiled_plan(rdmi_ctx* c, Builder& b, const Layout& L, std::map<std::string, int>& dense_off);
+int finish_tiled_plan(rdmi_ctx* c);
+void tiled_bind_params(rdmi_ctx* c);
 int build_fused_program(rdmi_ctx* c);
 
 // the device buffers both plans share: weight arena (wf floats, zeroed), pack-job table, embedding rows, sampler scratch
@@ -2079,13 +1716,7 @@ int do_repack(rdmi_ctx* c, hipStream_t s) {
             op.attn.gamma = P(c, op.p_gamma); op.attn.beta = P(c, op.p_beta); op.attn.b3 = P(c, op.p_b3);
         }
     }
-    for (auto& l : c->tl) {
-        if (l.kind == 6) { l.gact.gamma = P(c, l.p_gamma); l.gact.beta = P(c, l.p_beta); continue; }
-        if (l.kind != 0) continue;
-        l.conv.bias = l.p_bias.empty() ? c->d_w.get() + l.bias_arena : P(c, l.p_bias);
-        l.conv.gamma = l.p_gamma.empty() ? nullptr : P(c, l.p_gamma);
-        l.conv.beta = l.p_beta.empty() ? nullptr : P(c, l.p_beta);
-    }
+    if (c->tiled) tiled_bind_params(c);
     for (auto& q : c->progs) {
         if (!q.ok) continue;
         for (auto& f : q.fpatch) {
@@ -2117,7 +1748,12 @@ struct FwdIn {
     float* out; int NB;
     const float* tt_row = nullptr;        // sampler: precomputed time_mlp.2 output row (+ both biases) of this evaluation's t
     const float* dense_rows = nullptr;    // sampler: precomputed Dense_0 outputs [NB][dense_total] of this evaluation (skips the whole embedding)
+    float drop_p = 0.f; const unsigned long long* seed_dev = nullptr;   // tiled training forward: Dropout_0 probability and the step's seed word (null: no dropout)
 };
+
+}  // namespace
+#include "tiled_plan.h"
+namespace {
 
 int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
     const rdmi_arch& a = c->arch;
@@ -2163,7 +1799,7 @@ int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
     if (a.compute_dtype == 1 && !c->tiled && !c->in_train_forward)
         return fail("compute_dtype=bf16 on this shape is built for the TRAINING step only (model.train_dtype = 'bf16'); sampling and evaluation of the "
                     "GTO-Halo model run the exact-fp32 plans");
-    if (c->tiled) return run_tiled(c, f.x, f.x_mod, f.sig, f.sig_mod, f.t_is_time, f.t_scalar, f.smin, f.ratio, f.out, f.NB, f.dense_rows, s);
+    if (c->tiled) return run_tiled(c, f, s);
     // ---- the U-Net: one workgroup-resident launch (csrc/unet_kernel.h) ...
     const rdmi_ctx::FusedProg* fq = (c->use_fused && !c->debug_taps) ? c->pick(f.NB) : nullptr;
     if (c->in_train_forward) {      // one sample per workgroup pays while the batch fits the chip in about one wave of workgroups; beyond that the layer plan (bf16 MFMA) is faster
@@ -2226,125 +1862,6 @@ int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
             if (int e = launch_attn(aa, s)) return e;
         }
     }
-    return 0;
-}
-
-
-int run_tiled(rdmi_ctx* c, const float* x, int x_mod, const float* sig, int sig_mod, int sig_is_time, float t_scalar, float smin, float ratio, float* out, int NB,
-              const float* dense_rows, hipStream_t s) {
-    const rdmi_arch& a = c->arch;
-    const int HW = c->H * c->W, Cc = a.channels;
-    const long tot = (long)NB * HW * Cc;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, x, c->t_xin.get(), NB, HW, Cc, x_mod);
-    for (auto& l : c->tl) {
-        if (l.kind == 0) {
-            TConvArgs ca = l.conv;
-            ca.NB = NB;
-            if (ca.dense && dense_rows) ca.dense = dense_rows;        // the sampler's per-update Dense_0 rows
-            if (l.out_is_final && a.scale_by_sigma) {               // h / time_cond (RD/models/ncsnpp.py:350-351)
-                if (sig) { ca.sig = sig; ca.sig_mod = sig_mod; ca.sig_is_time = sig_is_time; ca.smin = smin; ca.ratio = ratio; }
-                else ca.out_scale /= sig_is_time ? smin * powf(ratio, t_scalar) : t_scalar;
-            }
-            const unsigned tiles = (unsigned)ceil_div(ca.Ho, ca.TR);
-            // column tiles per wave (the workgroup covers 64 * nct channels: staging and its GroupNorm/SiLU arithmetic are shared), as
-            // long as the launch still has >= 2 workgroups per CU
-            int nct = 1;
-            for (int cand : {4, 2})
-                if (ca.Cout_pad >= 64 * cand && (long)tiles * NB * ceil_div(ca.Cout_pad, 64 * cand) >= c->tiled_min_wgs) { nct = cand; break; }
-            dim3 grid(tiles * (unsigned)NB, (unsigned)ceil_div(ca.Cout_pad, 64 * nct));
-            const bool h = a.compute_dtype == 1;
-            const size_t lds = l.pre ? tconv_pre_lds_bytes(ca) : h ? tconv_bf16_lds_bytes(ca) : tconv_lds_bytes(ca);
-#define RDMI_TCONV_PRE(NMT_, NCT_)                                                                                                    \
-    do {                                                                                                                              \
-        if (ca.ntap == 1) hipLaunchKernelGGL((tconv_pre_kernel<NMT_, NCT_, 1>), grid, dim3(RDMI_THREADS), lds, s, ca);                \
-        else hipLaunchKernelGGL((tconv_pre_kernel<NMT_, NCT_, 9>), grid, dim3(RDMI_THREADS), lds, s, ca);                             \
-    } while (0)
-            // implicit-GEMM form (iconv_kernel: 128 x 128 tiles over the whole batch's pixels) once the launch has a workgroup per CU
-            // (read at context creation -- off by default, see finish_tiled_plan; RDMI_ICONV_MIN_WGS: tests set the threshold to reach the kernel at fixture batches)
-            if (l.pre && ca.stride == 1 && !ca.up && ca.TR * ca.Wo == 64 && (ca.Ho * ca.Wo) % 64 == 0 && ca.Cout % 128 == 0 && ca.Cv % 64 == 0) {
-                const long M = (long)NB * ca.Ho * ca.Wo;
-                const dim3 g2((unsigned)((M + 127) / 128), (unsigned)(ca.Cout / 128));
-                if ((long)g2.x * g2.y >= c->iconv_min_wgs) {
-                    static const bool by_shape = std::getenv("RDMI_PROF_SHAPES") != nullptr;      // diagnostic: one profile row per conv shape
-                    ProfScope ps2(c, s, by_shape ? "iconv_kernel<bf16> " + std::to_string(ca.Wo) + "x" + std::to_string(ca.Ho) + " K" + std::to_string(ca.ntap * ca.Cv) + " N" + std::to_string(ca.Cout) + (ca.resid ? " +res" : "") : std::string("iconv_kernel<bf16>"), l.flops_per_sample * NB);
-                    if (ca.ntap == 1) hipLaunchKernelGGL((iconv_kernel<1>), g2, dim3(RDMI_THREADS), iconv_lds_bytes(), s, ca);
-                    else hipLaunchKernelGGL((iconv_kernel<9>), g2, dim3(RDMI_THREADS), iconv_lds_bytes(), s, ca);
-                    continue;
-                }
-            }
-            ProfScope ps(c, s, l.pre ? "tconv_pre_kernel<bf16>" : h ? "tconv_kernel<bf16>" : "tconv_kernel<fp32>", l.flops_per_sample * NB);
-            if (l.pre) {
-                if (l.nmt == 4) { if (nct == 4) RDMI_TCONV_PRE(4, 4); else if (nct == 2) RDMI_TCONV_PRE(4, 2); else RDMI_TCONV_PRE(4, 1); }
-                else { if (nct == 4) RDMI_TCONV_PRE(1, 4); else if (nct == 2) RDMI_TCONV_PRE(1, 2); else RDMI_TCONV_PRE(1, 1); }
-                continue;
-            }
-#undef RDMI_TCONV_PRE
-#define RDMI_TCONV(NMT_, NCT_)                                                                                                        \
-    do {                                                                                                                              \
-        if (h) hipLaunchKernelGGL((tconv_kernel<NMT_, NCT_, true>), grid, dim3(RDMI_THREADS), lds, s, ca);                            \
-        else if (ca.drop_p > 0.f) hipLaunchKernelGGL((tconv_kernel<NMT_, NCT_, false, true>), grid, dim3(RDMI_THREADS), lds, s, ca);  \
-        else hipLaunchKernelGGL((tconv_kernel<NMT_, NCT_, false>), grid, dim3(RDMI_THREADS), lds, s, ca);                             \
-    } while (0)
-            if (l.nmt == 4) { if (nct == 4) RDMI_TCONV(4, 4); else if (nct == 2) RDMI_TCONV(4, 2); else RDMI_TCONV(4, 1); }
-            else { if (nct == 4) RDMI_TCONV(1, 4); else if (nct == 2) RDMI_TCONV(1, 2); else RDMI_TCONV(1, 1); }
-#undef RDMI_TCONV
-        } else if (l.kind == 1) {
-            ProfScope ps(c, s, "gn_stats_kernel", 0);
-            hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)l.G, (unsigned)NB), dim3(RDMI_THREADS), 16, s, l.sA, l.sB, l.CA, l.CB, l.HW, l.G, 1e-6f, l.stats);
-        } else if (l.kind == 2) {
-            ProfScope ps(c, s, a.compute_dtype == 1 ? "bgemm_nt_bf16_kernel" : "bgemm_nt_kernel", l.flops_per_sample * NB);
-            if (a.compute_dtype == 1) hipLaunchKernelGGL(bgemm_nt_bf16_kernel, dim3((unsigned)ceil_div(l.gemm.M, 64), (unsigned)ceil_div(l.gemm.N, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, l.gemm);
-            else hipLaunchKernelGGL(bgemm_nt_kernel, dim3((unsigned)ceil_div(l.gemm.M, 64), (unsigned)ceil_div(l.gemm.N, 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, l.gemm);
-        } else if (l.kind == 7) {
-            FlashArgs fa = l.flash; fa.NB = NB;
-            ProfScope ps(c, s, "flash_attn_bf16_kernel", l.flops_per_sample * NB);
-            const dim3 grid((unsigned)(fa.L / 64), (unsigned)NB);
-            static bool flash_attr = false;                          // 70 KB of dynamic LDS at C = 256
-            if (!flash_attr) {
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_bf16_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_bf16_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                flash_attr = true;
-            }
-            if (l.flashC == 256) hipLaunchKernelGGL(flash_attn_bf16_kernel<256>, grid, dim3(RDMI_THREADS), flash_lds_bytes<256>(), s, fa);
-            else if (l.flashC == 128) hipLaunchKernelGGL(flash_attn_bf16_kernel<128>, grid, dim3(RDMI_THREADS), flash_lds_bytes<128>(), s, fa);
-            else hipLaunchKernelGGL(flash_attn_bf16_kernel<64>, grid, dim3(RDMI_THREADS), flash_lds_bytes<64>(), s, fa);
-        } else if (l.kind == 6) {
-            GnActArgs g = l.gact; g.NB = NB;
-            if (l.fin) {
-                ProfScope ps(c, s, "gn_act_fin_kernel", 0);
-                hipLaunchKernelGGL(gn_act_fin_kernel, dim3((unsigned)ceil_div(g.HW, GA_PIX), (unsigned)(g.Cv / 64), (unsigned)NB), dim3(RDMI_THREADS), gn_act_fin_lds_bytes(std::max(g.tilesA, g.tilesB)), s, g);
-                continue;
-            }
-            const long units = (long)NB * g.HW * (g.Cv / 8);
-            ProfScope ps(c, s, "gn_act_kernel", 0);
-            hipLaunchKernelGGL(gn_act_kernel, dim3((unsigned)((units + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, g);
-        } else if (l.kind == 5) {
-            ProfScope ps(c, s, "gn_finalize_kernel", 0);
-            hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)NB), dim3(RDMI_THREADS), 0, s, l.sA, l.sB, l.CA, l.CB, l.tL, l.tC, l.pxA, l.pxB, l.HW, l.G, 1e-6f, l.stats);
-        } else if (l.kind == 3) {
-            const long rows = l.rows_per_sample * NB;
-            ProfScope ps(c, s, "softmax_rows_kernel", 0);
-            hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(RDMI_THREADS), 0, s, l.sm, rows, l.L, l.Lp);
-        } else if (l.kind == 8) {
-            ResizeArgs ra = l.rs; ra.NB = NB;
-            const long n = (long)NB * ra.Hd * ra.Wd * (ra.C / 4);
-            ProfScope ps(c, s, "nearest_resize_kernel", 0);
-            hipLaunchKernelGGL(nearest_resize_kernel, dim3((unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, ra);
-        } else {
-            const long n = (long)NB * l.tLp * l.tC;
-            ProfScope ps(c, s, "transpose_lc_kernel", 0);
-            if (l.t16 && l.tL % 64 == 0 && l.tC % 64 == 0)
-                hipLaunchKernelGGL(transpose_lc_tile16_kernel, dim3((unsigned)(l.tL / 64), (unsigned)(l.tC / 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s,
-                                   reinterpret_cast<const bf16_t*>(l.tsrc), reinterpret_cast<bf16_t*>(l.tdst), l.tL, l.tC, l.tld, l.tc0);
-            else if (l.t16) return fail("bf16 q | k | v: the transpose needs L and C in multiples of 64");
-            else if (l.tL % 64 == 0 && l.tC % 64 == 0)
-                hipLaunchKernelGGL(transpose_lc_tile_kernel, dim3((unsigned)(l.tL / 64), (unsigned)(l.tC / 64), (unsigned)NB), dim3(RDMI_THREADS), 0, s, l.tsrc, l.tdst, l.tL, l.tC, l.tld, l.tc0);
-            else
-            hipLaunchKernelGGL(transpose_lc_kernel, dim3((unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, l.tsrc, l.tdst, NB, l.tL, l.tC, l.tld, l.tc0, l.tLp);
-        }
-    }
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((tot + RDMI_THREADS - 1) / RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)c->t_out.get(), out, NB, HW, Cc, 0);
-    HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -2421,9 +1938,9 @@ const char* rdmi_path_info(rdmi_ctx* c) {
     static thread_local std::string s;
     if (!c) return "";
     if (c->tiled) {
-        s = std::string("tiled (") + (c->arch.compute_dtype == 1 ? "bf16 MFMA operands, fp32 accumulate" : "fp32") + "): " + std::to_string(c->tl.size()) + " launches over HBM-resident NHWC tensors (" + std::to_string(c->t_ws_per_sample * 4 / 1024) + " KiB of activations per sample)";
+        s = std::string("tiled (") + (c->arch.compute_dtype == 1 ? "bf16 MFMA operands, fp32 accumulate" : "fp32") + "): " + std::to_string(c->tiled->launches.size()) + " launches over HBM-resident NHWC tensors (" + std::to_string(c->tiled->ws_per_sample * 4 / 1024) + " KiB of activations per sample)";
         long n_resize = 0;
-        for (auto& l : c->tl) n_resize += l.kind == 8;
+        for (auto& l : c->tiled->launches) n_resize += std::holds_alternative<TResizeL>(l.op);
         s += "; resize launches (h onto an odd skip grid): " + std::to_string(n_resize);
     } else if (c->fused_ready() && c->use_fused && !c->debug_taps) {
         s = "fused: workgroup-resident U-Net, " + std::to_string(c->progs[0].fprog.size()) + " ops, " + std::to_string(c->progs[0].fused_lds) + " B LDS";
@@ -2986,9 +2503,10 @@ int rdmi_get_tap(rdmi_ctx* c, const char* name, float* dst, size_t dst_numel, in
     hipStream_t s = (hipStream_t)stream;
     const std::string nm(name);
     if (c->tiled) {      // the tiled plan never reuses a tensor: the output of a block is its last conv (Conv_1 / NIN_3)
-        for (auto it = c->tl.rbegin(); it != c->tl.rend(); ++it) {
-            if (it->kind != 0 || !(it->name == nm || it->name == nm + ".Conv_1" || it->name == nm + ".NIN_3")) continue;
-            const TConvArgs& a = it->conv;
+        for (auto it = c->tiled->launches.rbegin(); it != c->tiled->launches.rend(); ++it) {
+            const TConvL* cv = std::get_if<TConvL>(&it->op);
+            if (!cv || !(it->name == nm || it->name == nm + ".Conv_1" || it->name == nm + ".NIN_3")) continue;
+            const TConvArgs& a = cv->a;
             if (C) *C = a.Cout; if (H) *H = a.Ho; if (W) *W = a.Wo;
             const size_t per = (size_t)a.Cout * a.Ho * a.Wo;
             const int nb = (int)std::min<size_t>(dst_numel / per, (size_t)c->max_batch);

@@ -1,39 +1,32 @@
 // Training step on the TILED plan (fp32; shapes beyond one workgroup per sample, e.g. the CIFAR-shape model of BASELINE config #5).
 // Included by rdmi.hip after train_plan.h; rdmi_enable_training / rdmi_train_forward / rdmi_backward branch here on c->tiled.
 //
-// Forward: the ordinary tiled forward (run_tiled), with Dropout_0 applied in the GroupNorm+SiLU staging of every res block's Conv_1
-// (TConvArgs::drop_p: Philox mask of (step seed in device memory, launch index, source element)).  The tiled workspace is never
-// reused (TiledBuilder::talloc only grows), so every tensor the backward needs -- layer inputs, GroupNorm statistics, softmax
+// Forward: the ordinary tiled forward (run_tiled), handed the step's dropout probability and seed word (FwdIn::drop_p / seed_dev): the
+// launch loop applies Dropout_0 in the GroupNorm+SiLU staging of the convs flagged TConvL::dropout (every res block's Conv_1; Philox
+// mask of (step seed in device memory, launch index, source element)).  The plan itself is not written to.  The tiled workspace is
+// never reused (TiledBuilder::talloc only grows), so every tensor the backward needs -- layer inputs, GroupNorm statistics, softmax
 // probabilities -- is still in place afterwards.
 // Backward: the launch list in reverse into a gradient twin of the workspace (same offsets), zeroed once per step: every
 // launch ADDS its input gradients into the twin, so a tensor read by several launches (skip tensors, the residual stream)
 // collects their sum; the gradient of a conv's output is complete when its producer is reached.  Kernels: tiled_bwd_kernels.h.
+// What the backward needs to know about a launch is on its record (csrc/tiled_plan.h), written when the plan was built: a TConvL
+// carries the indices and layout of its weight / bias / GroupNorm parameters (TConvParams) and its dropout flag, the P V launch of
+// an attention block carries the index of its Q K^T launch (TBgemmL::qk).  Launch names are not consulted.
 #pragma once
 #include "tiled_bwd_kernels.h"
 
 namespace {
 
-struct TiledConvBwd {
-    int li = -1;                                       // launch index in c->tl
-    int pw[3] = {-1, -1, -1}, pb[3] = {-1, -1, -1};    // weight / bias parameters (q | k | v projection: three NIN matrices)
-    int co_blk = 0; long w_co = 0, w_ci = 0, w_t = 0;  // parameter layout: OIHW (3x3) or NIN [in][out]
-    int pg = -1, pbeta = -1;                           // GroupNorm gamma / beta
-    bool dropout = false;                              // Conv_1 of a res block: Dropout_0 on its activated input
-};
-
 struct TiledTrain {
-    std::map<int, TiledConvBwd> conv;                  // by launch index
-    dev_ptr<float> gws;                                // gradient twin of the tiled workspace (t_ws_per_sample * max_batch floats)
+    dev_ptr<float> gws;                                // gradient twin of the tiled workspace (ws_per_sample * max_batch floats)
     dev_ptr<float> gfin;                               // NHWC gradient of the network output
     dev_ptr<float> act, dact, wslab, cs, gred, gslab;
     static constexpr int MAX_SPLIT = 16;               // weight-gradient K splits (slab depth)
     int last_B = 0; float drop_p = 0.f;
 };
 
-bool ends_with(const std::string& s, const char* t) { const size_t n = std::strlen(t); return s.size() >= n && s.compare(s.size() - n, n, t) == 0; }
-
 inline float* tl_gptr(rdmi_ctx* c, const TiledTrain& tt, size_t off) {
-    if (off == rdmi_ctx::TLaunch::NONE || off == rdmi_ctx::TLaunch::XIN) return nullptr;
+    if (off == T_NONE || off == T_XIN) return nullptr;
     return tt.gws.get() + off * (size_t)c->max_batch;
 }
 
@@ -46,40 +39,22 @@ int tiled_enable_training(rdmi_ctx* c, TrainPlan& T) {
     T.ptotal = 0;
     for (size_t i = 0; i < c->params.size(); ++i) { T.poff[i] = T.ptotal; T.ptotal += c->params[i].numel; }
     size_t act_f = 1, dact_f = 1, slab_f = 1; int cmax = 64;
-    for (size_t li = 0; li < c->tl.size(); ++li) {
-        const rdmi_ctx::TLaunch& l = c->tl[li];
-        if (l.kind == 6 || l.kind == 7 || l.pre) return fail("tiled training: launch %s is a bf16-plan launch", l.name.c_str());
-        if (l.kind != 0) continue;
-        const TConvArgs& a = l.conv;
+    for (const TLaunch& tl : c->tiled->launches) {
+        const TConvL* l = std::get_if<TConvL>(&tl.op);
+        if (std::holds_alternative<TGnActL>(tl.op) || std::holds_alternative<TFlashL>(tl.op) || (l && l->pre)) return fail("tiled training: launch %s is a bf16-plan launch", tl.name.c_str());
+        if (!l) continue;
+        const TConvArgs& a = l->a;
         const int Cin = a.CA + a.CB;
-        TiledConvBwd b; b.li = (int)li;
-        if (ends_with(l.name, ".qkv")) {
-            const std::string pre = l.name.substr(0, l.name.size() - 4);
-            b.co_blk = a.Cout / 3; b.w_co = 1; b.w_ci = b.co_blk; b.w_t = 0;
-            for (int i = 0; i < 3; ++i) {
-                b.pw[i] = c->pindex.at(pre + ".NIN_" + std::to_string(i) + ".W");
-                b.pb[i] = c->pindex.at(pre + ".NIN_" + std::to_string(i) + ".b");
-            }
-        } else if (a.ntap == 1) {
-            b.pw[0] = c->pindex.at(l.name + ".W"); b.pb[0] = c->pindex.at(l.p_bias);
-            b.co_blk = a.Cout; b.w_co = 1; b.w_ci = a.Cout; b.w_t = 0;
-        } else {
-            b.pw[0] = c->pindex.at(l.name + ".weight"); b.pb[0] = c->pindex.at(l.p_bias);
-            b.co_blk = a.Cout; b.w_co = (long)Cin * 9; b.w_ci = 9; b.w_t = 1;
-        }
-        if (!l.p_gamma.empty()) {
-            if (a.up || a.stride != 1) return fail("tiled training: GroupNorm ahead of a resampling conv (%s)", l.name.c_str());
-            b.pg = c->pindex.at(l.p_gamma); b.pbeta = c->pindex.at(l.p_beta);
+        if (l->p_gamma >= 0) {
+            if (a.up || a.stride != 1) return fail("tiled training: GroupNorm ahead of a resampling conv (%s)", tl.name.c_str());
             act_f = std::max(act_f, (size_t)a.Hv * a.Wv * Cin);
         }
-        b.dropout = ends_with(l.name, ".Conv_1");
-        if (!l.in_is_x) dact_f = std::max(dact_f, (size_t)a.Hv * a.Wv * Cin);
+        if (!l->in_is_x) dact_f = std::max(dact_f, (size_t)a.Hv * a.Wv * Cin);
         slab_f = std::max(slab_f, (size_t)a.ntap * a.Cout * Cin * TiledTrain::MAX_SPLIT);
         cmax = std::max(cmax, std::max(a.Cout, Cin));
-        tt->conv[(int)li] = b;
     }
     const size_t E = (size_t)c->H * c->W * c->arch.channels, Mp = (size_t)pad16(c->max_batch);
-    HIP_OK(hip_alloc(tt->gws, c->t_ws_per_sample * NBmax));
+    HIP_OK(hip_alloc(tt->gws, c->tiled->ws_per_sample * NBmax));
     HIP_OK(hip_alloc(tt->gfin, E * NBmax));
     HIP_OK(hip_alloc(tt->act, act_f * NBmax));
     HIP_OK(hip_alloc(tt->dact, dact_f * NBmax));
@@ -115,28 +90,20 @@ int tiled_train_forward(rdmi_ctx* c, TrainPlan& T, const float* x, const float* 
     T.seed_slot = (T.seed_slot + 1) & 63;
     T.h_seed.get()[T.seed_slot] = seed;
     HIP_OK(hipMemcpyAsync(T.d_seed.get(), T.h_seed.get() + T.seed_slot, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-    for (auto& kv : tt.conv)
-        if (kv.second.dropout) {
-            TConvArgs& a = c->tl[(size_t)kv.first].conv;
-            a.drop_p = dropout_p; a.op_id = (uint32_t)kv.first; a.seed_dev = T.d_seed.get();
-        }
     FwdIn f{x, 0, T.sig_copy.get(), 0, 0.f, 0, 0.f, 0.f, labels ? T.lab_copy.get() : nullptr, B, out, B};
+    f.drop_p = dropout_p; f.seed_dev = T.d_seed.get();
     const int e = run_forward(c, f, s);
-    for (auto& kv : tt.conv) { TConvArgs& a = c->tl[(size_t)kv.first].conv; a.drop_p = 0.f; a.seed_dev = nullptr; }   // sampling stays p = 0
     if (c->profiling) prof_collect(c);
     tt.last_B = B; tt.drop_p = dropout_p; T.last_B = B;
     return e;
 }
 
-inline unsigned tb_blocks(long n) { return (unsigned)((n + RDMI_THREADS - 1) / RDMI_THREADS); }
-
 // backward of one conv launch: G (in place) -> bias / Dense_0 -> weight gradient -> data gradient -> GroupNorm / resampling adjoint.
 // grads_flat == null (VJP-only): the launches that feed only parameter gradients are left out (bias / Dense_0 sums, the activation
 // recompute and the weight-gradient contraction with its slab reduce, the gamma / beta row sums).  grad_x != null: the input conv's
 // data gradient goes straight to the caller's NCHW grad_x (input_dgrad_kernel; no gradient twin of the input exists).
-int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ctx::TLaunch& l, const TiledConvBwd& b, float* grads_flat, float* grad_x, int NB,
-                        hipStream_t s) {
-    const TConvArgs& a = l.conv;
+int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const TConvL& l, int li, float* grads_flat, float* grad_x, int NB, hipStream_t s) {
+    const TConvArgs& a = l.a; const TConvParams& b = l.w;
     const int Cin = a.CA + a.CB, HWo = a.Ho * a.Wo, HWv = a.Hv * a.Wv;
     const bool want_p = grads_flat != nullptr;
     auto pgrad = [&](int pi) -> float* { return pi >= 0 ? grads_flat + T.poff[(size_t)pi] : nullptr; };
@@ -152,17 +119,17 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
         hipLaunchKernelGGL(tb_bias_kernel, dim3((unsigned)ceil_div(a.Cout, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.cs.get(), NB, a.Cout,
                            pgrad(b.pb[0]), pgrad(b.pb[1]), pgrad(b.pb[2]), b.co_blk, l.use_dense ? T.gdense.get() : (float*)nullptr, c->dense_total, a.dense_off);
     }
-    const bool gn = b.pg >= 0;
+    const bool gn = l.p_gamma >= 0;
     TbGnArgs g{};
     g.A = a.srcA; g.B = a.srcB; g.CA = a.CA; g.CB = a.CB; g.HW = a.Ha * a.Wa; g.NB = NB;
     g.stats = a.stats; g.G = a.G; g.Cg = a.Cg; g.act = a.act; g.gamma = a.gamma; g.beta = a.beta;
-    g.drop_p = b.dropout ? tt.drop_p : 0.f; g.op_id = (uint32_t)b.li; g.seed_dev = T.d_seed.get();
+    g.drop_p = l.dropout ? tt.drop_p : 0.f; g.op_id = (uint32_t)li; g.seed_dev = T.d_seed.get();
     g.ACT = tt.act.get(); g.dACT = tt.dact.get(); g.red = tt.gred.get(); g.gslab = tt.gslab.get();
     g.gA = tl_gptr(c, tt, l.oA); g.gB = tl_gptr(c, tt, l.oB);
     g.up = a.up; g.Hv = a.Hv; g.Wv = a.Wv; g.has_gn = gn ? 1 : 0;
     if (gn && want_p) {   // the activated input, recomputed (GroupNorm + SiLU + the step's dropout mask): only the weight gradient reads it
         ProfScope ps(c, s, "tb_act_kernel", 0);
-        hipLaunchKernelGGL(tb_act_kernel, dim3(tb_blocks((long)NB * HWv * Cin)), dim3(RDMI_THREADS), 0, s, g);
+        hipLaunchKernelGGL(tb_act_kernel, grid1d((long)NB * HWv * Cin), dim3(RDMI_THREADS), 0, s, g);
     }
     if (want_p) {   // weight gradient: K = samples x output pixels split into <= MAX_SPLIT chunks, slab summed in a fixed order
         TbGemmArgs w{};
@@ -181,7 +148,7 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
             hipLaunchKernelGGL(tb_gemm_kernel<2>, dim3((unsigned)ceil_div(a.Cout, 64), (unsigned)ceil_div(Cin, 64), (unsigned)(a.ntap * ns)), dim3(RDMI_THREADS), 0, s, w);
         }
         ProfScope ps(c, s, "tb_wgrad_reduce_kernel", 0);
-        hipLaunchKernelGGL(tb_wgrad_reduce_kernel, dim3(tb_blocks((long)a.ntap * a.Cout * Cin)), dim3(RDMI_THREADS), 0, s, (const float*)tt.wslab.get(), ns, a.ntap,
+        hipLaunchKernelGGL(tb_wgrad_reduce_kernel, grid1d((long)a.ntap * a.Cout * Cin), dim3(RDMI_THREADS), 0, s, (const float*)tt.wslab.get(), ns, a.ntap,
                            a.Cout, Cin, pgrad(b.pw[0]), pgrad(b.pw[1]), pgrad(b.pw[2]), b.co_blk, b.w_co, b.w_ci, b.w_t);
     }
     if (l.in_is_x) return grad_x ? launch_input_dgrad(c, G, 0, grad_x, NB, s) : 0;   // the network input: only on request
@@ -203,29 +170,29 @@ int tiled_conv_backward(rdmi_ctx* c, TrainPlan& T, TiledTrain& tt, const rdmi_ct
         }
         if (want_p) {
             ProfScope ps(c, s, "tb_rowsum_kernel", 0);
-            hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 0, pgrad(b.pg));
-            hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 1, pgrad(b.pbeta));
+            hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 0, pgrad(l.p_gamma));
+            hipLaunchKernelGGL(tb_rowsum_kernel, dim3((unsigned)ceil_div(Cin, RDMI_THREADS)), dim3(RDMI_THREADS), 0, s, (const float*)tt.gslab.get(), NB, Cin, 2, 1, pgrad(l.p_beta));
         }
     }
     ProfScope ps(c, s, "tb_src_grad_kernel", 0);
-    hipLaunchKernelGGL(tb_src_grad_kernel, dim3(tb_blocks((long)NB * a.Ha * a.Wa * Cin)), dim3(RDMI_THREADS), 0, s, g);
+    hipLaunchKernelGGL(tb_src_grad_kernel, grid1d((long)NB * a.Ha * a.Wa * Cin), dim3(RDMI_THREADS), 0, s, g);
     return 0;
 }
 
 // AttnBlockpp core backward on the stored probabilities P (launch `pv`; q | k | v from launch `qk`):
 //   dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dP o P)), dQ = alpha dS K, dK = alpha dS^T Q   (dP / dS live in the twin of S)
-int tiled_attn_backward(rdmi_ctx* c, TiledTrain& tt, const rdmi_ctx::TLaunch& qk, const rdmi_ctx::TLaunch& pv, int NB, hipStream_t s) {
+int tiled_attn_backward(rdmi_ctx* c, TiledTrain& tt, const TBgemmL& qk, const TBgemmL& pv, int NB, hipStream_t s) {
     // Lp: row stride of P and of its twin (L rounded up to whole K steps of the forward's P V; == L when L % 16 == 0).  Every contraction
     // here runs over L, and dP / dS are written over [L][L] only: the pad columns of the twin stay at the zeros of the step's memset and
     // never reach dQ or dK.
-    const int L = pv.gemm.M, C = pv.gemm.N, Lp = pv.gemm.lda;
+    const int L = pv.a.M, C = pv.a.N, Lp = pv.a.lda;
     const long C3 = 3L * C, LL = (long)L * Lp, LC3 = L * C3, LC = (long)L * C;
     const float* P = tl_ptr(c, pv.oA);
     const float* qkv = tl_ptr(c, qk.oA);
     float* dS = tl_gptr(c, tt, pv.oA);
     const float* dO = tl_gptr(c, tt, pv.oC);
     float* dqkv = tl_gptr(c, tt, qk.oA);
-    const float alpha = qk.gemm.alpha;
+    const float alpha = qk.a.alpha;
     auto gemm = [&](int M, int N, int K, const float* A, long ab, long am, long ak, const float* B, long bb, long bk, long bn, float* Cp, long cb, long cm, long cn,
                     float al) {
         TbGemmArgs g{};
@@ -253,28 +220,24 @@ int tiled_backward(rdmi_ctx* c, TrainPlan& T, const float* grad_out, float* grad
     const size_t NBmax = (size_t)c->max_batch;
     const int HW = c->H * c->W, Cc = c->arch.channels;
     // every parameter gradient below is a store; time_embed.W (not trained) stays zero.  The twin takes sums: zeroed (all of it,
-    // t_ws_per_sample * max_batch floats -- the tensors are [tensor][sample] blocks, so the first NB samples are not one range)
+    // ws_per_sample * max_batch floats -- the tensors are [tensor][sample] blocks, so the first NB samples are not one range)
     if (grads_flat) HIP_OK(hipMemsetAsync(grads_flat, 0, T.ptotal * sizeof(float), s));
-    HIP_OK(hipMemsetAsync(tt.gws.get(), 0, c->t_ws_per_sample * NBmax * sizeof(float), s));
+    HIP_OK(hipMemsetAsync(tt.gws.get(), 0, c->tiled->ws_per_sample * NBmax * sizeof(float), s));
     if (grads_flat) HIP_OK(hipMemsetAsync(T.gdense.get(), 0, (size_t)pad16(c->max_batch) * c->dense_total * sizeof(float), s));
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(tb_blocks((long)NB * HW * Cc)), dim3(RDMI_THREADS), 0, s, grad_out, tt.gfin.get(), NB, HW, Cc, 0);
-    for (int li = (int)c->tl.size() - 1; li >= 0; --li) {
-        const rdmi_ctx::TLaunch& l = c->tl[(size_t)li];
-        if (l.kind == 0) {
-            if (int e = tiled_conv_backward(c, T, tt, l, tt.conv.at(li), grads_flat, grad_x, NB, s)) return e;
-        } else if (l.kind == 2 && ends_with(l.name, ".pv")) {
-            const std::string qk_name = l.name.substr(0, l.name.size() - 3) + ".qk";
-            int qi = li - 1;
-            while (qi >= 0 && c->tl[(size_t)qi].name != qk_name) --qi;
-            if (qi < 0) return fail("tiled training: no launch %s", qk_name.c_str());
-            if (int e = tiled_attn_backward(c, tt, c->tl[(size_t)qi], l, NB, s)) return e;
-        } else if (l.kind == 8) {   // nearest resize of h onto the skip grid: its twin is complete here (every reader comes later in the list)
-            ResizeArgs ra = l.rs; ra.NB = NB;
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid1d((long)NB * HW * Cc), dim3(RDMI_THREADS), 0, s, grad_out, tt.gfin.get(), NB, HW, Cc, 0);
+    const std::vector<TLaunch>& tl = c->tiled->launches;
+    for (int li = (int)tl.size() - 1; li >= 0; --li) {
+        if (const TConvL* l = std::get_if<TConvL>(&tl[(size_t)li].op)) {
+            if (int e = tiled_conv_backward(c, T, tt, *l, li, grads_flat, grad_x, NB, s)) return e;
+        } else if (const TBgemmL* pv = std::get_if<TBgemmL>(&tl[(size_t)li].op)) {
+            if (pv->qk >= 0) { if (int e = tiled_attn_backward(c, tt, std::get<TBgemmL>(tl[(size_t)pv->qk].op), *pv, NB, s)) return e; }
+        } else if (const TResizeL* l = std::get_if<TResizeL>(&tl[(size_t)li].op)) {   // nearest resize of h onto the skip grid: its twin is complete here (every reader comes later in the list)
+            ResizeArgs ra = l->a; ra.NB = NB;
             ProfScope ps(c, s, "tb_resize_bwd_kernel", 0);
-            hipLaunchKernelGGL(tb_resize_bwd_kernel, dim3(tb_blocks((long)NB * ra.Hs * ra.Ws * ra.C)), dim3(RDMI_THREADS), 0, s, ra, (const float*)tl_gptr(c, tt, l.oOut),
-                               tl_gptr(c, tt, l.oA));
+            hipLaunchKernelGGL(tb_resize_bwd_kernel, grid1d((long)NB * ra.Hs * ra.Ws * ra.C), dim3(RDMI_THREADS), 0, s, ra, (const float*)tl_gptr(c, tt, l->oDst),
+                               tl_gptr(c, tt, l->oSrc));
         }
-        // kinds 1 / 5 (GroupNorm statistics): their gradient is part of the GroupNorm backward; 3 / 4 and `qk`: inside the attention backward
+        // GroupNorm statistics (TStatsL / TStatsRecL): their gradient is part of the GroupNorm backward; softmax, transpose and Q K^T: inside the attention backward
         HIP_OK(hipGetLastError());
     }
     if (grads_flat) { if (int e = embed_backward(c, T, grads_flat, NB, s)) return e; }
