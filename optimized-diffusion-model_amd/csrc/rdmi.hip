@@ -130,7 +130,7 @@ struct Op {
     bool has_mapA = false, has_mapSc = false;
     // packed weight locations (floats into the weight arena)
     size_t w_off = 0, wsc_off = 0, w3_off = 0, bqkv_off = 0;
-    std::string p_gamma, p_beta, p_bias, p_bias_sc, p_b3;
+    int p_gamma = -1, p_beta = -1, p_bias = -1, p_bias_sc = -1, p_b3 = -1;   // parameter indices (-1: none), resolved when the plan is built
     ConvSpec spec;               // OP_CONV: what was asked for
     int attn_C = 0, attn_H = 0, attn_W = 0;
     bool dropout = false;        // train mode applies Dropout_0 to this op's activated input (Conv_1 of a resblock)
@@ -139,6 +139,7 @@ struct Op {
 struct ProfEntry { std::string name; double ms = 0; long launches = 0; double flops = 0; };
 struct TrainPlan;                        // csrc/train_plan.h
 struct TiledPlan;                        // csrc/tiled_plan.h
+struct FusedPlan;                        // csrc/fused_plan.h
 
 }  // namespace
 
@@ -167,44 +168,12 @@ struct rdmi_ctx {
     dev_ptr<float> d_tt, d_th1; int tt_cap = 0;                 // sampler: time-path rows of all updates (rdmi_pc_sample)
     dev_ptr<float> d_dense_all; size_t dense_all_cap = 0;      // sampler: Dense_0 outputs of a chunk of updates [U][NBm][dense_total]
     dev_ptr<StepState> d_state;
-    // fused (workgroup-resident) path: one program per samples-per-workgroup value
-    bool use_fused = true;
-    dev_ptr<long long> d_stamps;         // diagnostic (RDMI_STAMPS=1), shared by the programs that record stamps
-    struct FPatch { int op; int field; std::string param; size_t arena_off; };
-    struct FusedProg {
-        int S = 1; bool ok = false; std::string why;     // why: the reason the program could not be built (the layer plan runs instead)
-        std::vector<FOp> fprog;              // host copy; parameter pointers are patched at repack time
-        std::vector<FPatch> fpatch; std::vector<short> ftabs;
-        std::vector<std::string> fdesc;      // one line per fused op
-        dev_ptr<FOp> d_fprog; dev_ptr<short> d_ftabs; dev_ptr<float> d_spill; size_t spill_per_sample = 0;
-        UnetArgs fargs{}; size_t fused_lds = 0;
-        bool coop = false; int n_xchg = 0; dev_ptr<unsigned long long> d_xbuf; dev_ptr<int> d_coop_err; int max_nb = 0;     // co-operative program
-        bool train = false;                  // the training forward's program (stashes every layer output, applies Dropout_0): never picked for inference
-    };
+    bool use_fused = true;               // RDMI_PATH=layers: the layer plan runs although the fused programs exist
+    std::unique_ptr<FusedPlan> fused;    // the workgroup-resident programs of a context that does not run the tiled plan (csrc/fused_plan.h)
     std::unique_ptr<TiledPlan> tiled;    // non-null: the context runs the tiled plan (shapes whose samples do not fit one workgroup: csrc/tiled_plan.h)
     bool in_train_forward = false;       // set around run_forward by rdmi_train_forward
     dev_ptr<bf16_t> d_w16;               // bf16 copies of the forward conv weights (training with compute_dtype = bf16)
-    std::vector<FusedProg> progs;
-    int s_min_wg = 256;                            // a program with S samples per workgroup is used from batch s_min_wg * S (RDMI_S_MIN_WG: tests)
-    bool use_coop = true;                          // RDMI_COOP=0: never select the co-operative program (A/B, tests)
-    int coop_stride = 1;                           // ids of a group's members are this far apart (RDMI_COOP_STRIDE).  1: under round-robin placement member m of every
-                                                   // group sits on XCDs m and m + 4, so an XCD's L2 only ever holds ITS quarter of the shared weights (2.5 MB: it stays
-                                                   // resident from one launch to the next); 8 would put a whole group on one XCD (cheaper exchanges, 4x the weights per L2).
-                                                   // Measured at B = 128: 821 vs 837 us per update.  Speed only: the exchange is correct under any placement.
-    unsigned coop_epoch = 0;                       // tag base of the next co-operative launch
-    int last_prog = 0;                             // index in progs of the program the last forward ran (diagnostics)
-    const FusedProg* pick(int NB) const {
-        // a batch that leaves CUs to spare at one sample per workgroup and fits the chip in ONE wave of workgroups: the co-operative
-        // program (groups of four CUs share the low-resolution weights); larger batches: the program with the most samples per
-        // workgroup that still fills the chip
-        if (use_coop) for (auto& q : progs) if (q.ok && q.coop && !q.train && NB <= q.max_nb) return &q;
-        const FusedProg* best = nullptr;
-        for (auto& q : progs) if (q.ok && !q.coop && !q.train && (q.S == 1 || NB >= s_min_wg * q.S) && (!best || q.S > best->S)) best = &q;
-        return best;
-    }
-    bool fused_ready() const { return !progs.empty() && progs[0].ok; }
     float train_drop_p = 0.f; const unsigned long long* train_seed_dev = nullptr;      // set around the training forward's launch
-    int train_prog = -1;                           // index in progs of the training forward's program (-1: the layer plan runs the training forward)
     std::map<std::string, size_t> wmap;  // packed-weight arena offsets by parameter prefix
     bool packed_valid = false;
     bool debug_taps = false;
@@ -214,7 +183,7 @@ struct rdmi_ctx {
     std::vector<int> ev_entry;
     size_t ev_used = 0;
     std::unique_ptr<TrainPlan> train;    // rdmi_enable_training (csrc/train_plan.h)
-    ~rdmi_ctx();                         // defined after train_plan.h: TiledPlan and TrainPlan are complete there
+    ~rdmi_ctx();                         // defined after train_plan.h: TiledPlan, FusedPlan and TrainPlan are complete there
 };
 
 namespace {
@@ -323,7 +292,7 @@ void build_params(rdmi_ctx* c, const Layout& L) {
 // plan builder
 // ------------------------------------------------------------------------------------------
 // Shapes for which the 3x3 conv after a nearest-x2 upsample runs folded into four 2x2 phase convs in the inference programs of the
-// workgroup-resident kernel (FusedBuilder::conv_up4): a 4x4 source (a phase = one 16-row MFMA tile), a square weight, input channels in
+// workgroup-resident kernel (fused_plan.h: FusedBuilder::conv_up4): a 4x4 source (a phase = one 16-row MFMA tile), a square weight, input channels in
 // whole groups of 128 (the single-tile tap-major loop with the 8-deep weight ring).  RDMI_NO_UP_FOLD=1 keeps the nine-tap op everywhere.
 // Asked by the layer plan (does the folded packing exist?) and by the program builder (does this op fold?): one rule for both.
 inline bool up_fold_shape_ok(int Hs, int Ws, int Cin, int Cout) {
@@ -455,9 +424,9 @@ struct Builder {
         if (op.has_mapSc) { op.mapSc_off = ints.size(); ints.insert(ints.end(), op.mapSc.begin(), op.mapSc.end()); }
         // weights
         op.w_off = pack_conv(s.conv, Cin, s.Cout);
-        op.p_bias = s.conv + ".bias";
-        if (!s.gn.empty()) { op.p_gamma = s.gn + ".weight"; op.p_beta = s.gn + ".bias"; }
-        if (a.Csc) { op.wsc_off = pack_nin(s.nin, s.CscA + s.CscB, s.Cout); op.p_bias_sc = s.nin + ".b"; }
+        op.p_bias = c->pindex.at(s.conv + ".bias");
+        if (!s.gn.empty()) { op.p_gamma = c->pindex.at(s.gn + ".weight"); op.p_beta = c->pindex.at(s.gn + ".bias"); }
+        if (a.Csc) { op.wsc_off = pack_nin(s.nin, s.CscA + s.CscB, s.Cout); op.p_bias_sc = c->pindex.at(s.nin + ".b"); }
         op.flops_per_sample = 2.0 * a.HWo * s.Cout * (9.0 * Cin + (s.CscA + s.CscB));
         use(s.tA); use(s.tB); use(s.tScA); use(s.tScB); use(s.tRes);
         int out = -1;
@@ -546,8 +515,8 @@ struct Builder {
         c->wmap[name + ".bqkv"] = op.bqkv_off;
         for (int i = 0; i < 3; ++i) job_copy(name + ".NIN_" + std::to_string(i) + ".b", op.bqkv_off, C, i * C);
         op.w3_off = pack_nin(name + ".NIN_3", C, C);
-        op.p_b3 = name + ".NIN_3.b";
-        op.p_gamma = name + ".GroupNorm_0.weight"; op.p_beta = name + ".GroupNorm_0.bias";
+        op.p_b3 = c->pindex.at(name + ".NIN_3.b");
+        op.p_gamma = c->pindex.at(name + ".GroupNorm_0.weight"); op.p_beta = c->pindex.at(name + ".GroupNorm_0.bias");
         op.flops_per_sample = 2.0 * (4.0 * a.L * C * C + 2.0 * a.L * a.L * C);
         op.attn_C = C; op.attn_H = H; op.attn_W = W;
         use(tin);
@@ -589,7 +558,7 @@ int add_resblock(Builder& b, const std::string& name, int tA, int tB, int CA, in
 int build_tiled_plan(rdmi_ctx* c, Builder& b, const Layout& L, std::map<std::string, int>& dense_off);
 int finish_tiled_plan(rdmi_ctx* c);
 void tiled_bind_params(rdmi_ctx* c);
-int build_fused_program(rdmi_ctx* c);
+int build_fused_program(rdmi_ctx* c, const std::map<std::string, int>& dense_off);   // csrc/fused_plan.h
 
 // the device buffers both plans share: weight arena (wf floats, zeroed), pack-job table, embedding rows, sampler scratch
 int alloc_arenas(rdmi_ctx* c, size_t wf) {
@@ -800,805 +769,7 @@ int build_plan(rdmi_ctx* c) {
             aa.wqkv = w + op.w_off; aa.bqkv = w + op.bqkv_off; aa.w3 = w + op.w3_off;
         }
     }
-    return build_fused_program(c);
-}
-
-// ------------------------------------------------------------------------------------------
-// fused program (workgroup-resident U-Net, csrc/unet_kernel.h)
-// ------------------------------------------------------------------------------------------
-struct FusedBuilder {
-    rdmi_ctx* c;
-    rdmi_ctx::FusedProg& prog;                 // the program being built
-    static constexpr int LDS_TOTAL = 160 * 1024;
-    struct Blk { int off, size; };
-    std::vector<Blk> freel;
-    int arena_lo = 0, high_water = 0;
-    std::map<std::string, int> tabcache;       // geometry key -> encoded table reference (region << 24 | offset in shorts)
-    std::vector<short> tabs1;                  // region 1: tables of the multi-sample (low-resolution) section, resident in LDS only during it
-    int tab1_lds = 0;                          // LDS byte offset of region 1 (an arena block of the low-resolution section)
-    struct LT { int off = -1, C = 0, H = 0, W = 0, rs = 0, bytes = 0, ns = 1; bool pm = false; int hw() const { return H * W; } int rows() const { return ns * H * W; } };
-    // pm: the rows are PHASE-MAJOR (output of the folded upsample conv, conv_up4): pixel (2y + py, 2x + px) of the H x W grid sits in row
-    // (2 py + px) * (H/2 * W/2) + y * W/2 + x.  Readers go through a row map (gather_cat) -- no op takes such a tensor as a plain grid.
-    static int pm_row(int H, int W, int y, int x) { return (2 * (y & 1) + (x & 1)) * ((H / 2) * (W / 2)) + (y / 2) * (W / 2) + x / 2; }
-    int S = 1;                      // samples per workgroup of the program being built
-    bool coop = false;              // co-operative program: S = 4 samples per GROUP of four workgroups (unet_kernel.h: fop_conv_coop)
-    bool train = false;             // training forward: stash every layer-plan tensor, Dropout_0 in the fused GroupNorm_1 epilogues
-    std::map<std::string, int> lp_tensor, lp_op;      // layer-plan tensor / op indices by name (train)
-    int n_xchg = 0;                 // exchanges emitted so far
-    int xslot_granules = 0;         // largest exchanged block, in 8-byte granules
-    struct PendX { bool on = false; LT t; } pendx;      // output of the last co-operative 3x3 conv: exchanged before the next op is emitted
-    int cur_samp = 0;               // sample slot the emitted ops belong to; -1: ops cover all S samples (low-resolution section)
-    int multi_slot_off = -1;        // LDS offset of the per-(sample, group) partial-sum slots of multi-sample fused GroupNorms
-    int ns_now() const { return cur_samp < 0 ? S : 1; }
-    int shift_of(int hw) { int sh = 0; while ((1 << sh) < hw) ++sh; if (cur_samp < 0 && (1 << sh) != hw) fail_("multi-sample ops need a power-of-two pixel count"); return cur_samp < 0 ? sh : 0; }
-    size_t spill_floats = 0;
-    bool failed = false;
-    std::string why;
-    int gn_slot_off = 0;            // LDS byte offset of the fused-GroupNorm partial-sum slots (2 KiB)
-    bool gn_fuse = true;            // RDMI_NO_GNFUSE=1 keeps every GroupNorm its own op (A/B and debugging)
-    int n_gn_fused = 0, n_gn_ops = 0;
-
-    void fail_(const std::string& m) { if (!failed) { failed = true; why = m; } }
-
-    // ---- LDS arena: first-fit with coalescing free list
-    void arena_init(int lo) { arena_lo = lo; freel.clear(); freel.push_back({lo, LDS_TOTAL - lo}); high_water = lo; }
-    int alloc_bytes(int n) {
-        n = (n + 15) & ~15;
-        for (size_t i = 0; i < freel.size(); ++i)
-            if (freel[i].size >= n) {
-                const int o = freel[i].off;
-                freel[i].off += n; freel[i].size -= n;
-                if (freel[i].size == 0) freel.erase(freel.begin() + (long)i);
-                high_water = std::max(high_water, o + n);
-                return o;
-            }
-        {
-            std::string fl;
-            for (auto& f : freel) fl += " [" + std::to_string(f.off) + "+" + std::to_string(f.size) + "]";
-            fail_("LDS arena exhausted at op " + std::to_string(prog.fprog.size()) + " (need " + std::to_string(n) + " B; free:" + fl + ")");
-        }
-        return arena_lo;
-    }
-    int alloc_top(int n) {                      // odd-sized scratch (Vt, P): carve from the END of the highest block that fits
-        n = (n + 15) & ~15;
-        for (size_t k = freel.size(); k-- > 0;)
-            if (freel[k].size >= n) {
-                const int o = freel[k].off + freel[k].size - n;
-                freel[k].size -= n;
-                if (freel[k].size == 0) freel.erase(freel.begin() + (long)k);
-                high_water = std::max(high_water, o + n);
-                return o;
-            }
-        return alloc_bytes(n);
-    }
-    void free_bytes(int off, int n) {
-        n = (n + 15) & ~15;
-        freel.push_back({off, n});
-        std::sort(freel.begin(), freel.end(), [](const Blk& a, const Blk& b) { return a.off < b.off; });
-        for (size_t i = 0; i + 1 < freel.size();)
-            if (freel[i].off + freel[i].size == freel[i + 1].off) { freel[i].size += freel[i + 1].size; freel.erase(freel.begin() + (long)i + 1); }
-            else ++i;
-    }
-    LT talloc(int C, int H, int W) {
-        LT t; t.C = C; t.H = H; t.W = W; t.ns = ns_now(); t.rs = C + 4; t.bytes = t.ns * H * W * t.rs * 4; t.off = alloc_bytes(t.bytes);
-        return t;
-    }
-    void tfree(LT& t) { if (t.off >= 0) free_bytes(t.off, t.bytes); t.off = -1; }
-
-    // ---- row tables (int16), deduplicated by geometry
-    int add_table(const std::string& key, const std::vector<short>& v) {
-        auto it = tabcache.find(key);
-        if (it != tabcache.end()) return it->second;
-        const int region = (S > 1 && cur_samp < 0) ? 1 : 0;
-        std::vector<short>& tb = region ? tabs1 : prog.ftabs;
-        while (tb.size() % 2) tb.push_back(-1);
-        const int off = (int)tb.size() | (region << 24);
-        tb.insert(tb.end(), v.begin(), v.end());
-        tabcache[key] = off;
-        return off;
-    }
-    // tap table of a conv reading tensor (Hs x Ws) seen as a virtual (Hv x Wv) grid (nearest), output (Ho x Wo)
-    int tap_table(int Hs, int Ws, int Hv, int Wv, int Ho, int Wo, int stride, int pad_lo, int tap) {
-        char key[128];
-        const int ns = ns_now();                       // multi-sample: block-diagonal (row s*HWo + p reads source row s*HWs + ...)
-        snprintf(key, sizeof key, "tap:%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", Hs, Ws, Hv, Wv, Ho, Wo, stride, pad_lo, tap, ns);
-        const int Mpad = pad16(ns * Ho * Wo);
-        std::vector<short> v((size_t)Mpad, (short)-1);
-        for (int m = 0; m < ns * Ho * Wo; ++m) {
-            const int sm = m / (Ho * Wo), pm = m % (Ho * Wo);
-            const int oy = pm / Wo, ox = pm % Wo;
-            const int iy = oy * stride + tap / 3 - pad_lo, ix = ox * stride + tap % 3 - pad_lo;
-            if (iy < 0 || iy >= Hv || ix < 0 || ix >= Wv) continue;
-            const int sy = std::min((int)std::floor(iy * ((float)Hs / Hv)), Hs - 1);
-            const int sx = std::min((int)std::floor(ix * ((float)Ws / Wv)), Ws - 1);
-            v[(size_t)m] = (short)(sm * Hs * Ws + sy * Ws + sx);
-        }
-        return add_table(key, v);
-    }
-    int ident_table(int M) {
-        const int Mpad = pad16(M);
-        std::vector<short> v((size_t)Mpad, (short)-1);
-        for (int m = 0; m < M; ++m) v[(size_t)m] = (short)m;
-        return add_table("id:" + std::to_string(M), v);
-    }
-    int map_table(int Hs, int Ws, int Hd, int Wd, bool pm = false) {      // nearest map as a GATHER row map (pm: onto a phase-major source, LT::pm)
-        std::vector<short> v((size_t)Hd * Wd);
-        for (int y = 0; y < Hd; ++y)
-            for (int x = 0; x < Wd; ++x) {
-                const int sy = std::min((int)std::floor(y * ((float)Hs / Hd)), Hs - 1);
-                const int sx = std::min((int)std::floor(x * ((float)Ws / Wd)), Ws - 1);
-                v[(size_t)y * Wd + x] = (short)(pm ? pm_row(Hs, Ws, sy, sx) : sy * Ws + sx);
-            }
-        char key[64];
-        snprintf(key, sizeof key, "map:%d,%d,%d,%d,%d", Hs, Ws, Hd, Wd, pm ? 1 : 0);
-        return add_table(key, v);
-    }
-    // Tap table t = 2 ty + tx of the folded upsample conv over a source of Hs x Ws = 16 pixels: entry [16 p + i] is the source row that tap
-    // (ty, tx) of phase p = 2 py + px reads for source pixel i = y * Ws + x, i.e. pixel (y + ty - 1 + py, x + tx - 1 + px), or -1 (zero row).
-    // An upsampled pixel lies outside the 2Hs x 2Ws grid exactly when its source pixel lies outside Hs x Ws: the padding carries over.
-    int up4_table(int Hs, int Ws, int tap) {
-        std::vector<short> v((size_t)4 * Hs * Ws, (short)-1);
-        for (int p = 0; p < 4; ++p)
-            for (int y = 0; y < Hs; ++y)
-                for (int x = 0; x < Ws; ++x) {
-                    const int sy = y + (tap >> 1) - 1 + (p >> 1), sx = x + (tap & 1) - 1 + (p & 1);
-                    if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) v[(size_t)p * Hs * Ws + y * Ws + x] = (short)(sy * Ws + sx);
-                }
-        char key[64];
-        snprintf(key, sizeof key, "up4:%d,%d,%d", Hs, Ws, tap);
-        return add_table(key, v);
-    }
-
-    // ---- op emission.  Table offsets are emitted in SHORTS relative to the table region and turned into LDS
-    //      byte offsets once the region's base is known (finish()).
-    FOp blank(int kind) {
-        FOp o;
-        std::memset(&o, 0, sizeof o);
-        o.kind = kind; o.a_off = -1; o.b_off = -1; o.a_map_off = -1; o.dense_off = -1; o.resid_off = -1; o.scale = 1.f; o.src_off = -1; o.gn_off = -1; o.samp = cur_samp; o.drop_op = -1;
-        return o;
-    }
-    int emit(const FOp& o) { flush_xchg(); prog.fprog.push_back(o); return (int)prog.fprog.size() - 1; }
-    // all-gather of tensor t (column slices of 32 per member) between the four members; t2: a second tensor of the same shape
-    int emit_xchg(const LT& t, const LT* own_rows_src) {
-        FOp o = blank(FOP_XCHG);
-        o.dst_off = t.off; o.dst_rs = t.rs; o.xidx = n_xchg++;
-        if (own_rows_src) {          // row slices: every member contributes its sample's rows (all columns)
-            o.a_hw = 1; o.rows = own_rows_src->hw(); o.C = t.C; o.a_off = own_rows_src->off; o.a_rs = own_rows_src->rs;
-            if (own_rows_src->C != t.C || t.rows() != 4 * o.rows) fail_("exchange: row-slice shapes");
-        } else {
-            o.a_hw = 0; o.rows = t.rows(); o.C = t.C / 4;
-        }
-        if (o.C < 32 || o.C > 128 || (o.C & (o.C - 1)) || o.rows * o.C > 512) fail_("exchange: block of " + std::to_string(o.rows) + " x " + std::to_string(o.C));
-        xslot_granules = std::max(xslot_granules, 2 * o.rows * o.C);      // room for a second tensor (<= 1024 granules = 512 pairs: one per thread)
-        prog.fprog.push_back(o);
-        return (int)prog.fprog.size() - 1;
-    }
-    void flush_xchg() { if (pendx.on) { pendx.on = false; emit_xchg(pendx.t, nullptr); } }
-    enum { F_GAMMA, F_BETA, F_BIAS, F_BIAS2, F_W, F_SC0W, F_SC1W, F_BIAS_ARENA };
-    void patch_param(int op, int field, const std::string& param) { prog.fpatch.push_back({op, field, param, 0}); }
-    void patch_arena(int op, int field, size_t off) { prog.fpatch.push_back({op, field, "", off}); }
-
-    void gather_x(const LT& dst) {               // network input -> LDS [HW][16+4]
-        FOp o = blank(FOP_GATHER);
-        o.dst_off = dst.off; o.dst_rs = dst.rs; o.rows = dst.rows(); o.C = dst.C;
-        o.CA = c->arch.channels; o.CB = 0; o.a_off = -2; o.a_hw = dst.hw(); o.hw_shift = shift_of(dst.hw());
-        emit(o);
-    }
-    // dst = a tensor parked in this workgroup's spill slot `spill` ([n][hw][C]); single- or multi-sample by the current mode
-    void gather_g(const LT& dst, size_t spill) {
-        FOp o = blank(FOP_GATHER);
-        o.dst_off = dst.off; o.dst_rs = dst.rs; o.rows = dst.rows(); o.C = dst.C;
-        o.CA = dst.C; o.CB = 0; o.a_off = -1; o.a_hw = dst.hw(); o.a_mod = 0; o.hw_shift = shift_of(dst.hw());
-        const int idx = emit(o);
-        spill_fix.push_back({idx, spill, 2});
-    }
-    // dst = concat(A (LDS tensor, nearest-mapped onto dst's grid), B (global spill slot))
-    void gather_cat(const LT& dst, const LT& A, size_t spillB, int CB) {
-        FOp o = blank(FOP_GATHER);
-        o.dst_off = dst.off; o.dst_rs = dst.rs; o.rows = dst.rows(); o.C = dst.C;
-        o.CA = A.C; o.CB = CB; o.a_off = A.off; o.a_rs = A.rs; o.a_hw = A.hw(); o.hw_shift = shift_of(dst.hw());
-        if (A.H != dst.H || A.W != dst.W || A.pm) o.a_map_off = map_table(A.H, A.W, dst.H, dst.W, A.pm);
-        if (A.pm && A.ns != 1) fail_("phase-major tensors are single-sample");
-        o.b_off = -1;
-        const int idx = emit(o);
-        spill_fix.push_back({idx, spillB, 1});
-    }
-    void copy_t(const LT& dst, const LT& src) {
-        if (src.pm) fail_("copy of a phase-major tensor");
-        FOp o = blank(FOP_GATHER);
-        o.dst_off = dst.off; o.dst_rs = dst.rs; o.rows = dst.rows(); o.C = dst.C;
-        o.CA = src.C; o.CB = 0; o.a_off = src.off; o.a_rs = src.rs; o.a_hw = src.hw(); o.hw_shift = shift_of(dst.hw());
-        emit(o);
-    }
-    struct SpillFix { int op; size_t off; int which; };      // which: 0 STORE destination, 1 GATHER source B, 2 GATHER source A
-    // Per-sample sections of a multi-sample program are emitted once per sample slot: the spill slots they use must be the
-    // SAME for every slot (the buffer is [slot][n][rows][C]); the first emission records them, the others replay them.
-    std::vector<size_t> slot_log; size_t slot_pos = 0; bool slot_replay = false;
-    std::vector<SpillFix> spill_fix;
-    size_t spill_store(const LT& t) {            // LDS tensor -> this workgroup's slot of the spill buffer
-        if (t.pm) fail_("spill of a phase-major tensor");
-        FOp o = blank(FOP_STORE);
-        o.dst_off = t.off; o.dst_rs = t.rs; o.rows = t.rows(); o.C = t.C; o.hw_shift = shift_of(t.hw());
-        const int idx = emit(o);
-        size_t off;
-        if (slot_replay) { if (slot_pos >= slot_log.size()) { fail_("spill replay out of slots"); return 0; } off = slot_log[slot_pos++]; }
-        else { off = spill_floats; spill_floats += (size_t)t.hw() * t.C; slot_log.push_back(off); }
-        spill_fix.push_back({idx, off, 0});
-        return off;
-    }
-    // GroupNorm (+SiLU) of tensor t (in place), or of `src` into t (copy form).  When the tensor being normalised is the
-    // output of the CONV op emitted just before (only STOREs in between), has 4-channel groups and the conv's tiling gives
-    // every wave a single pass, the GroupNorm is folded into that conv's epilogue (FOp::gn_*) and no op is emitted.
-    bool try_fuse_gn(const LT& t, const std::string& pre, bool act, const LT* src) {
-        if (!gn_fuse) return false;
-        const LT& in = src ? *src : t;
-        int j = (int)prog.fprog.size() - 1, jx = -1;
-        while (j >= 0 && (prog.fprog[(size_t)j].kind == FOP_STORE || prog.fprog[(size_t)j].kind == FOP_XCHG)) { if (prog.fprog[(size_t)j].kind == FOP_XCHG) jx = j; --j; }
-        if (j < 0) return false;
-        FOp& p = prog.fprog[(size_t)j];
-        if (p.coop && !pendx.on && (jx < 0 || prog.fprog[(size_t)jx].dst_off != in.off || prog.fprog[(size_t)jx].src_off >= 0)) return false;
-        if (p.kind != FOP_CONV || p.dst_kind != 0 || p.gn_off >= 0 || p.dst_off != in.off || p.dst_rs != in.rs) return false;
-        if (p.Cout != t.C || p.rows != t.rows() || t.C % 4 != 0 || std::min(t.C / 4, 32) * 4 != t.C) return false;      // Cg == 4 only
-        const int ntiles = p.Cout_pad >> 4;
-        const int lWN = (ntiles >= 8 && (ntiles & 7) == 0) ? 3 : (ntiles >= 4 ? 2 : (ntiles >= 2 ? 1 : 0));      // as fop_conv
-        const int WN = 1 << lWN, WM = UW_WAVES >> lWN;
-        if (ntiles > WN || p.mtiles > 4 * WM) return false;                    // a wave would make several passes
-        const int nslots = p.samp >= 0 ? WM * 4 : 4;
-        if (p.samp >= 0) { if ((t.C / 4) * nslots * 8 > 1024) return false; }
-        else if (multi_slot_off < 0 || t.ns * (t.C / 4) * 32 > 4096 || (t.hw() != 16 && t.hw() != 4)) return false;
-        p.gn_off = t.off; p.gn_rs = t.rs; p.gn_act = act ? 1 : 0; p.gn_raw = src ? 1 : 0;
-        p.gn_slot_off = p.samp >= 0 ? gn_slot_off : multi_slot_off; p.gn_nslots = nslots;
-        p.eps = 1e-6f; p.inv_cnt = 1.0f / (float)(4 * t.hw());
-        patch_param(j, F_GAMMA, pre + ".weight"); patch_param(j, F_BETA, pre + ".bias");
-        ++n_gn_fused;
-        if (train && pre.size() > 12 && pre.compare(pre.size() - 12, 12, ".GroupNorm_1") == 0) {      // this activation is Conv_1's input: Dropout_0 acts on it
-            auto it = lp_op.find(pre.substr(0, pre.size() - 12));
-            if (it == lp_op.end()) fail_("training forward: no layer-plan op for " + pre);
-            else if (c->ops[(size_t)it->second].dropout) p.drop_op = it->second;
-        }
-        if (p.coop) {        // the conv now also produces the activated tensor (own columns): it has to travel too
-            if (pendx.on) {
-                if (src) { pendx.on = false; const int ix = emit_xchg(in, nullptr); prog.fprog[(size_t)ix].src_off = t.off; prog.fprog[(size_t)ix].src_rs = t.rs; }
-                // in-place form: the pending exchange of the conv's destination already carries the activated values
-            } else if (src) { prog.fprog[(size_t)jx].src_off = t.off; prog.fprog[(size_t)jx].src_rs = t.rs; }
-        }
-        return true;
-    }
-    void gn(const LT& t, const std::string& pre, bool act, const LT* src = nullptr) {
-        if (t.pm || (src && src->pm)) fail_("GroupNorm of a phase-major tensor");
-        if (try_fuse_gn(t, pre, act, src)) return;
-        if (train && pre.size() > 12 && pre.compare(pre.size() - 12, 12, ".GroupNorm_1") == 0) fail_("training forward: " + pre + " is not folded into its conv (Dropout_0 lives in that epilogue)");
-        ++n_gn_ops;
-        FOp o = blank(FOP_GN);
-        if (src) { o.src_off = src->off; o.src_rs = src->rs; }
-        o.dst_off = t.off; o.dst_rs = t.rs; o.rows = t.rows(); o.C = t.C;
-        o.G = std::min(t.C / 4, 32); o.act = act ? 1 : 0; o.eps = 1e-6f; o.hw_shift = shift_of(t.hw());
-        {
-            // multi-sample ops spread the ns * G (sample, group) pairs over the workgroup: T lanes per pair
-            const int pairs = t.ns * o.G, T = UW_THREADS / pairs, c4n = t.C / 4;
-            o.logT = T == 32 ? 5 : (T == 16 ? 4 : (T == 64 ? 6 : (T == 8 ? 3 : 2)));
-            o.logG = 0; while ((1 << o.logG) < o.G) ++o.logG;
-            o.Cg = t.C / o.G;
-            o.magic_c4n = (65536 + c4n - 1) / c4n; o.magic_Cg = (65536 + o.Cg - 1) / o.Cg;
-            o.inv_cnt = 1.0f / (float)(o.Cg * t.hw());
-            if ((1 << o.logT) != T || T * pairs != UW_THREADS) fail_("GroupNorm lanes-per-group not a power of two");
-            if ((1 << o.logG) != o.G) fail_("GroupNorm group count not a power of two");
-            if (t.ns * o.G * 8 > 1024) fail_("GroupNorm statistics of all samples exceed the scratch region");
-            if (ceil_div(t.hw(), T) > 6 || o.Cg > 8) fail_("GroupNorm group too large for the register-resident statistics");
-        }
-        if (t.C % o.G != 0 || UW_THREADS % o.G != 0 || UW_THREADS / o.G > 64) fail_("GroupNorm shape C=" + std::to_string(t.C));
-        const int idx = emit(o);
-        patch_param(idx, F_GAMMA, pre + ".weight"); patch_param(idx, F_BETA, pre + ".bias");
-    }
-    struct ConvOut { int kind; LT* t; };
-    // 3x3 conv (or 1x1 when ntap == 1) over LDS tensor `in`
-    int conv(const LT& in, int Hv, int Wv, int Ho, int Wo, int stride, int pad_lo, int ntap, const std::string& wkey,
-             size_t w_extra_off, int Cout, const std::string& bias_param, size_t bias_arena, int dst_kind, const LT* dst,
-             float scale, int dense_off, const LT* resid, const LT* sc_src, const std::string& sc_key,
-             const std::string& bias2_param) {
-        FOp o = blank(FOP_CONV);
-        const int ns = ns_now();
-        if (in.pm || (resid && resid->pm) || (dst && dst->pm)) fail_("conv over a phase-major tensor");
-        o.rows = ns * Ho * Wo; o.mtiles = pad16(o.rows) / 16; o.Cout = Cout; o.Cout_pad = pad16(Cout);
-        o.ntap = ntap; o.hw_shift = shift_of(Ho * Wo);
-        if (ns > 1 && dst_kind != 0) fail_("multi-sample convs write LDS tensors only");
-        o.main_ph.lds_off = in.off; o.main_ph.rs = in.rs; o.main_ph.nch = pad16(in.C) / 16;
-        if (in.C % 16 != 0) fail_("conv input channels not padded");
-        for (int t = 0; t < ntap; ++t)
-            o.tab_off[t] = ntap == 1 ? ident_table(ns * Ho * Wo) : tap_table(in.H, in.W, Hv, Wv, Ho, Wo, stride, pad_lo, t);
-        o.dense_off = dense_off; o.scale = scale; o.dst_kind = dst_kind;
-        if (dst) { o.dst_off = dst->off; o.dst_rs = dst->rs; }
-        if (resid) { o.resid_off = resid->off; o.resid_rs = resid->rs; }
-        if (o.mtiles > 6) fail_("conv with more than 96 output rows per workgroup");
-        if (sc_src) fail_("fused CONV ops carry no shortcut phases (the NIN shortcut is its own 1x1 op)");
-        if (sc_src) {
-            o.nsc = 1;
-            o.sc[0].lds_off = sc_src->off; o.sc[0].rs = sc_src->rs; o.sc[0].nch = sc_src->C / 16; o.sc[0].tab_off = ident_table(ns * Ho * Wo);
-        }
-        const int idx = emit(o);
-        patch_arena(idx, F_W, c->wmap.at(wkey) + w_extra_off);
-        if (!bias_param.empty()) patch_param(idx, F_BIAS, bias_param); else patch_arena(idx, F_BIAS_ARENA, bias_arena);
-        if (sc_src) { patch_arena(idx, F_SC0W, c->wmap.at(sc_key)); patch_param(idx, F_BIAS2, bias2_param); }
-        if (train) {                     // the layer plan keeps this conv's output under the name of its op: "<block>.Conv_0", "<block>" (Conv_1), the attention block, or the conv itself
-            std::string tn = wkey;
-            auto ends = [&](const char* suf) { const size_t n = std::strlen(suf); return tn.size() >= n && tn.compare(tn.size() - n, n, suf) == 0; };
-            if (ends(".Conv_1")) tn.resize(tn.size() - 7);
-            else if (ends(".NIN_3")) tn.resize(tn.size() - 6);
-            else if (ends(".NIN_0") || ends(".qkv3")) tn.clear();
-            else if (ends(".Conv_0") && (tn.rfind("downsample.", 0) == 0 || tn.rfind("upsample.", 0) == 0)) tn.resize(tn.size() - 7);
-            if (!tn.empty() && dst_kind == 0) {
-                auto it = lp_tensor.find(tn);
-                if (it == lp_tensor.end()) fail_("training forward: no layer-plan tensor '" + tn + "'");
-                else {
-                    const Tensor& t = c->tensors[(size_t)it->second];
-                    FOp& q = prog.fprog[(size_t)idx];
-                    if (t.C != Cout || t.H * t.W != q.rows) fail_("training forward: tensor '" + tn + "' has another shape");
-                    q.stash = c->ws.get() + t.off * (size_t)c->max_batch;
-                    q.stash_bf16 = c->arch.compute_dtype == 1 ? 1 : 0;
-                }
-            }
-            prog.fprog[(size_t)idx].drop_op = -1;
-        }
-        if (coop && cur_samp < 0) {      // low-resolution section of the co-operative program: column-sliced, K split over the waves
-            FOp& q = prog.fprog[(size_t)idx];
-            q.coop = 1;
-            if (q.Cout_pad != 128 || q.mtiles != 1 || q.main_ph.nch % 4 != 0 || dst_kind != 0 || !dst || dst->C != 128)
-                fail_("co-operative conv shape (Cout " + std::to_string(Cout) + ", " + std::to_string(q.mtiles) + " row tiles, " + std::to_string(q.main_ph.nch) + " chunks)");
-            if (ntap == 9) { pendx.on = true; pendx.t = *dst; }      // the next conv contracts over this tensor: all-gather it
-        }
-        return idx;
-    }
-    // Can the 3x3 conv over the nearest-x2 upsampled `in` run folded (conv_up4)?  Inference programs only: the training backward needs the
-    // unfolded weight gradient.  RDMI_NO_UP_FOLD=1 keeps the nine-tap op (A/B and debugging).
-    bool up_fold_ok(const LT& in, int Hv, int Wv, int Cout) const {
-        return !train && cur_samp >= 0 && !in.pm && Hv == 2 * in.H && Wv == 2 * in.W && up_fold_shape_ok(in.H, in.W, in.C, Cout) &&
-               c->wmap.count("upsample." + std::to_string(c->arch.n_levels - 2) + ".Conv_0.up4") != 0;
-    }
-    // The same conv as FOUR 2x2 convs on the source grid, one per output phase (py, px): output pixel (2y + py, 2x + px) reads source rows
-    // y - 1, y, y through the nearest map when py = 0 and y, y, y + 1 when py = 1 (columns alike), so the taps that share a source pixel
-    // have their weights summed once at repack time (pack kind 5) -- 4 taps instead of 9.  Each phase is one 16-row tile with its own four
-    // weight blocks (FOp::w_tile_stride); dst is written phase-major (LT::pm).
-    int conv_up4(const LT& in, const std::string& wkey, int Cout, const std::string& bias_param, LT* dst) {
-        FOp o = blank(FOP_CONV);
-        o.rows = 4 * in.hw(); o.mtiles = 4; o.Cout = Cout; o.Cout_pad = pad16(Cout);
-        o.ntap = 4; o.hw_shift = shift_of(o.rows);
-        o.main_ph.lds_off = in.off; o.main_ph.rs = in.rs; o.main_ph.nch = in.C / 16;
-        for (int t = 0; t < 4; ++t) o.tab_off[t] = up4_table(in.H, in.W, t);
-        o.w_tile_stride = 4 * in.C * o.Cout_pad * (int)sizeof(float);
-        o.dst_off = dst->off; o.dst_rs = dst->rs;
-        // fop_conv honours w_tile_stride only where a single-tile pass takes fconv_main_t<.., 1, false, 8>: chunks per tap in whole eights, more
-        // than 4 rows, a plain LDS destination; the packed block is square (kind 5 packs ch x ch)
-        if (o.main_ph.nch % 8 != 0 || o.rows <= 4 || o.dst_kind != 0 || in.C != Cout || in.hw() != 16 || in.pm || cur_samp < 0 || dst->C != Cout || dst->hw() != o.rows)
-            fail_("folded upsample conv: unsupported shape (" + std::to_string(in.H) + "x" + std::to_string(in.W) + " source, " + std::to_string(in.C) + " -> " + std::to_string(Cout) + " channels)");
-        dst->pm = true;
-        const int idx = emit(o);
-        patch_arena(idx, F_W, c->wmap.at(wkey + ".up4"));
-        patch_param(idx, F_BIAS, bias_param);
-        return idx;
-    }
-};
-
-// ResnetBlockDDPMpp on LDS tensors.  xin: raw block input (consumed).  Returns the block output.
-// When the block has a NIN shortcut (cin != cout, i.e. every concat-fed up block) the shortcut is evaluated FIRST
-// into the output buffer, so GroupNorm_0 can then run in place on xin: no second copy of the (large) concat
-// tensor is ever resident.  Identity-shortcut blocks keep xin raw for the residual and normalise a copy.
-FusedBuilder::LT fused_resblock(FusedBuilder& b, const std::string& name, FusedBuilder::LT& xin, int cout, int dense_off) {
-    using LT = FusedBuilder::LT;
-    const int H = xin.H, W = xin.W;
-    const float rs2 = (float)(1.0 / std::sqrt(2.0));
-    if (xin.C != cout) {
-        LT out = b.talloc(cout, H, W);
-        b.conv(xin, H, W, H, W, 1, 0, 1, name + ".NIN_0", 0, cout, name + ".NIN_0.b", 0, 0, &out, 1.f, -1, nullptr, nullptr, "", "");
-        b.gn(xin, name + ".GroupNorm_0", true);
-        LT h1 = b.talloc(cout, H, W);
-        b.conv(xin, H, W, H, W, 1, 1, 9, name + ".Conv_0", 0, cout, name + ".Conv_0.bias", 0, 0, &h1, 1.f, dense_off, nullptr, nullptr, "", "");
-        b.tfree(xin);
-        b.gn(h1, name + ".GroupNorm_1", true);
-        b.conv(h1, H, W, H, W, 1, 1, 9, name + ".Conv_1", 0, cout, name + ".Conv_1.bias", 0, 0, &out, rs2, -1, &out, nullptr, "", "");
-        b.tfree(h1);
-        return out;
-    }
-    LT xact = b.talloc(xin.C, H, W);
-    b.gn(xact, name + ".GroupNorm_0", true, &xin);
-    LT h1 = b.talloc(cout, H, W);
-    b.conv(xact, H, W, H, W, 1, 1, 9, name + ".Conv_0", 0, cout, name + ".Conv_0.bias", 0, 0, &h1, 1.f, dense_off, nullptr, nullptr, "", "");
-    b.tfree(xact);
-    b.gn(h1, name + ".GroupNorm_1", true);
-    LT out = b.talloc(cout, H, W);
-    b.conv(h1, H, W, H, W, 1, 1, 9, name + ".Conv_1", 0, cout, name + ".Conv_1.bias", 0, 0, &out, rs2, -1, &xin, nullptr, "", "");
-    b.tfree(h1);
-    b.tfree(xin);
-    return out;
-}
-
-// AttnBlockpp on an LDS tensor (consumed).  Returns the block output.
-FusedBuilder::LT fused_attn(FusedBuilder& b, const std::string& name, FusedBuilder::LT& x) {
-    using LT = FusedBuilder::LT;
-    rdmi_ctx* c = b.c;
-    const int C = x.C, H = x.H, W = x.W, L = H * W, Lpad = pad16(L);
-    if (C != 64 || Lpad > 96) { b.fail_("attention: only C=64, H*W<=96 is built"); return x; }
-    if (b.cur_samp < 0) { b.fail_("attention inside the multi-sample (low-resolution) section is not built"); return x; }
-    LT xn = b.talloc(C, H, W);
-    b.gn(xn, name + ".GroupNorm_0", false, &x);
-    // Inference programs fold NIN_3 into the value projection (weights packed as ".qkv3f" / ".bqkvf"): the attention op then writes
-    // (P V' + b3 + x) / sqrt2 itself and the 1x1 NIN_3 conv -- 10-15 k cycles of almost pure per-op overhead, five times per forward --
-    // disappears.  The training forward keeps the reference's op sequence (the backward needs the tensor between P V and NIN_3).
-    const bool fold3 = !b.train && std::getenv("RDMI_NO_ATTN_FOLD") == nullptr;
-    // ... and the k projection into q (k_fold_shape_ok; ".qv2f" / ".bqvf"): no k tensor, the attention op reads xn as K, so xn lives
-    // until after that op, in place of the k tensor of the same size.  (fop_attn clamps key rows to L - 1: nothing is asked of xn's rows beyond L.)
-    const bool foldk = fold3 && k_fold_shape_ok(C, L) && c->wmap.count(name + ".qv2f") != 0;
-    const int NP = foldk ? 2 : 3;
-    LT q = b.talloc(C, H, W), k = foldk ? xn : b.talloc(C, H, W);
-    const int ps = Lpad + 4;
-    const int vt_bytes = C * ps * 4, p_bytes = L * ps * 4;
-    const int vt_off = b.alloc_top(vt_bytes);
-    const size_t bq = c->wmap.at(name + (foldk ? ".bqvf" : fold3 ? ".bqkvf" : ".bqkv"));
-    {   // q, k, v in one contraction: the layer plan already packs NIN_0..2 side by side? no: [3][C/16][C][16] -> use the
-        // dedicated fused packing [C/16][3C][16] (wmap key ".qkv3"; [C/16][2C][16] under the k fold)
-        const int idx = b.conv(xn, H, W, H, W, 1, 0, 1, name + (foldk ? ".qv2f" : fold3 ? ".qkv3f" : ".qkv3"), 0, NP * C, "", bq, 3, &q, 1.f, -1, nullptr, nullptr, "", "");
-        FOp& o = b.prog.fprog[(size_t)idx];
-        o.dst2_off = foldk ? q.off : k.off; o.dst3_off = vt_off; o.dst3_rs = ps; o.split_C = C;
-        // the single-pass projection (fconv_qkv): the training kernel holds its three-projection form, the inference kernels the two-projection
-        // form only -- an inference program without the k fold (RDMI_NO_K_FOLD=1, numerical A/B) runs the generic split conv
-        o.qkv1 = (std::getenv("RDMI_NO_QKV1") == nullptr && (b.train || foldk) && o.ntap == 1 && o.main_ph.nch == 4 && o.Cout_pad == NP * 64 && C == 64 && o.mtiles <= 6) ? 1 : 0;
-        if (foldk && !o.qkv1) b.fail_("attention: the k-folded projection needs the single-pass form");
-    }
-    if (!foldk) b.tfree(xn);
-    const int p_off = b.alloc_top(p_bytes);
-    // Under the k fold x, xn, q, Vt and P are all live here (xn used to be gone by now): the output goes where q is -- the op reads q
-    // only in its score phase, which a barrier separates from the P V' phase that writes the output.
-    LT o = foldk ? q : b.talloc(C, H, W);
-    {
-        FOp a = b.blank(FOP_ATTN);
-        a.q_off = q.off; a.k_off = k.off; a.qk_rs = q.rs; a.k_rs = k.rs; a.vt_off = vt_off; a.p_off = p_off; a.ps = ps;
-        a.L = L; a.Lpad = Lpad; a.C = C; a.att_scale = 1.0f / std::sqrt((float)C);
-        a.dst_off = o.off; a.dst_rs = o.rs;
-        if (fold3) { a.resid_off = x.off; a.resid_rs = x.rs; a.scale = (float)(1.0 / std::sqrt(2.0)); }
-        const int ia = b.emit(a);
-        if (fold3) b.patch_param(ia, FusedBuilder::F_BIAS, name + ".NIN_3.b");
-    }
-    if (!foldk) b.tfree(q);
-    b.tfree(k);                                  // under the k fold: xn
-    b.free_bytes(vt_off, vt_bytes); b.free_bytes(p_off, p_bytes);
-    if (fold3) { b.tfree(x); return o; }
-    LT out = b.talloc(C, H, W);
-    b.conv(o, H, W, H, W, 1, 0, 1, name + ".NIN_3", 0, C, name + ".NIN_3.b", 0, 0, &out, (float)(1.0 / std::sqrt(2.0)), -1, &x, nullptr, "", "");
-    b.tfree(o);
-    b.tfree(x);
-    return out;
-}
-
-int build_fused_program_pass(rdmi_ctx* c, rdmi_ctx::FusedProg& q, int S, int TAB_RESERVE, int TAB1_RESERVE, int* tab_used, int* tab1_used, bool coop, bool train);
-
-// Two passes: the first sizes the row-table regions (and is dropped), the second builds the program with them sized exactly.
-int build_one_program(rdmi_ctx* c, int S, bool coop = false, bool train = false) {
-    int used = 0, used1 = 0;
-    {
-        rdmi_ctx::FusedProg sizing;
-        if (int e = build_fused_program_pass(c, sizing, S, 8 * 1024, 24 * 1024, &used, &used1, coop, train)) return e;
-    }
-    rdmi_ctx::FusedProg q;
-    if (int e = build_fused_program_pass(c, q, S, (used + 63) & ~63, (used1 + 63) & ~63, &used, &used1, coop, train)) return e;
-    c->progs.push_back(std::move(q));
-    return 0;
-}
-
-// How many workgroups of the fused kernel the device holds at once (one per CU: each takes the CU's whole LDS).
-int resident_workgroups() {
-#ifdef RDMI_EMU
-    return 256;
-#else
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    return cus;
-#endif
-}
-
-int build_fused_program(rdmi_ctx* c) {
-    // S = 1: one sample per workgroup (B <= 128 with guidance fills the 256 CUs exactly).  Larger batches run the
-    // low-resolution half of the network for S = 2 / 4 samples at once per workgroup: every streamed weight fragment then
-    // feeds S samples (that half is weight-stream bound at S = 1) and its per-op fixed cost is shared.
-    if (int e = build_one_program(c, 1)) return e;
-    const char* only = std::getenv("RDMI_S");           // RDMI_S=1 keeps the single-sample program only (A/B)
-    if (const char* e = std::getenv("RDMI_S_MIN_WG")) c->s_min_wg = std::max(1, atoi(e));
-    for (int S : {2, 4})
-        if (c->progs[0].ok && c->arch.n_levels >= 2 && c->max_batch >= c->s_min_wg * S && (!only || atoi(only) >= S))
-            if (int e = build_one_program(c, S)) return e;
-    // The co-operative program (groups of four workgroups share the low-resolution section): for batches that fit the chip in one
-    // wave of workgroups.  RDMI_COOP=0 leaves it out; RDMI_COOP_STRIDE sets the distance between a group's workgroup ids.
-    if (const char* e = std::getenv("RDMI_COOP")) c->use_coop = atoi(e) != 0;
-#ifdef RDMI_EMU
-    c->coop_stride = 1;          // the emulator runs consecutive workgroup ids concurrently
-#endif
-    if (const char* e = std::getenv("RDMI_COOP_STRIDE")) c->coop_stride = std::max(1, atoi(e));
-    if (c->progs[0].ok && c->use_coop && c->arch.n_levels >= 2 && !only)
-        if (int e = build_one_program(c, 4, true)) return e;
-    return 0;
-}
-
-int build_fused_program_pass(rdmi_ctx* c, rdmi_ctx::FusedProg& q, int S, int TAB_RESERVE, int TAB1_RESERVE, int* tab_used, int* tab1_used, bool coop, bool train) {
-    using LT = FusedBuilder::LT;
-    const rdmi_arch& a = c->arch;
-    q.S = S; q.train = train;
-    FusedBuilder b{c, q};
-    b.S = S; b.coop = coop; b.train = train;
-    if (train) {
-        for (size_t i = 0; i < c->tensors.size(); ++i) b.lp_tensor[c->tensors[i].name] = (int)i;
-        for (size_t i = 0; i < c->ops.size(); ++i) b.lp_op[c->ops[i].name] = (int)i;
-    }
-    const int nslot0 = coop ? 1 : S;                  // how often the full-resolution sections are emitted (co-operative: the member's own sample only)
-    Layout L = build_layout(c);
-    std::map<std::string, int> dense_off;
-    {
-        int dt = 0;
-        for (auto& d : L.down) { dense_off[d.name] = dt; dt += d.cout; }
-        dense_off["mid_block1"] = dt; dt += L.mid_ch;
-        dense_off["mid_block2"] = dt; dt += L.mid_ch;
-        for (auto& u : L.up) { dense_off[u.name] = dt; dt += u.cout; }
-    }
-    // LDS: [row tables] [zero row] [GN stats] [tensor arena]
-    const int zero_bytes = 1280;                     // >= (Cmax/16)*64 + 64 for Cmax = 256... host-checked below
-    const int stat_bytes = 1024 + 64;                         // GN op scratch [S][2 x 32] overlaid with the fused-GroupNorm partial-sum slots (never live together)
-    b.arena_init(TAB_RESERVE + zero_bytes + stat_bytes);
-    b.gn_slot_off = TAB_RESERVE + zero_bytes;
-    b.gn_fuse = std::getenv("RDMI_NO_GNFUSE") == nullptr;
-    const int H0 = c->H, W0 = c->W;
-    if (H0 * W0 > 96) { q.why = "more than 96 pixels per sample"; return 0; }
-    const int nlev = a.n_levels;
-    const bool multi = S > 1;
-
-    struct HS { size_t spill; int C, H, W; };
-    std::vector<HS> hs;                               // the skip stack (RD/models/ncsnpp.py:268-292, 311-338)
-    int ch = a.nf, H = H0, W = W0;
-    size_t hand_down = 0, hand_up = 0;                // multi-sample: level-0 <-> low-resolution hand-off slots
-    LT h;
-    // ---- level 0, down path: once per sample slot (same LDS, same spill slots)
-    const int nrb = a.num_res_blocks;
-    for (int sl = 0; sl < nslot0; ++sl) {
-        b.cur_samp = sl;
-        b.slot_replay = sl > 0; b.slot_pos = 0;
-        H = H0; W = W0; ch = a.nf;
-        LT xin = b.talloc(16, H, W);
-        b.gather_x(xin);
-        h = b.talloc(a.nf, H, W);
-        b.conv(xin, H, W, H, W, 1, 1, 9, "input_conv", 0, a.nf, "input_conv.bias", 0, 0, &h, 1.f, -1, nullptr, nullptr, "", "");
-        b.tfree(xin);
-        if (sl == 0) hs.push_back({(size_t)-1, a.nf, H, W});          // hs[0] (input_conv output) is never popped (RD/models/ncsnpp.py:268,315)
-        for (int j = 0; j < nrb; ++j) {
-            const BlockSpec& bs = L.down[(size_t)j];
-            h = fused_resblock(b, bs.name, h, bs.cout, dense_off[bs.name]);
-            ch = bs.cout;
-            if (bs.attn) h = fused_attn(b, "down_attn." + std::to_string(j), h);
-            const size_t sp = b.spill_store(h);
-            if (sl == 0) hs.push_back({sp, ch, H, W});
-        }
-        if (sl == 0) hs.push_back(hs.back());
-        if (nlev > 1) {
-            const int Ho = (H + 1 - 3) / 2 + 1, Wo = (W + 1 - 3) / 2 + 1;
-            LT o = b.talloc(ch, Ho, Wo);
-            const std::string nm = "downsample.0.Conv_0";
-            b.conv(h, H, W, Ho, Wo, 2, 0, 9, nm, 0, ch, nm + ".bias", 0, 0, &o, 1.f, -1, nullptr, nullptr, "", "");
-            b.tfree(h);
-            h = o; H = Ho; W = Wo;
-            if (multi && !coop) { hand_down = b.spill_store(h); b.tfree(h); }
-        }
-    }
-    b.slot_replay = false;
-    // ---- levels >= 1 (down), bottleneck, levels >= 1 (up): all S samples at once when S > 1.
-    //      Co-operative program: only the levels of at most 4 pixels per sample (and the bottleneck) run in the shared form -- that
-    //      part is bound by the weight stream and by 4-row MFMA tiles with one sample per CU; the 4x4 level is matrix-pipe bound
-    //      either way (measured: sharing it costs more in exchanges than it saves) and stays per sample like level 0.
-    int d = nrb, u = 0, loadtab_idx = -1;
-    {
-        b.cur_samp = (multi && !coop) ? -1 : 0;
-        int loadtab_op = -1;
-        bool in_coop = false;
-        auto enter_multi = [&]() {
-            b.multi_slot_off = b.alloc_top(4096);
-            b.tab1_lds = b.alloc_top(TAB1_RESERVE);
-            FOp lt = b.blank(FOP_LOADTAB);            // the section's row tables: global -> LDS (source / size patched below)
-            lt.dst_off = b.tab1_lds;
-            loadtab_op = b.emit(lt);
-        };
-        auto leave_multi = [&]() {
-            b.free_bytes(b.multi_slot_off, 4096);
-            b.multi_slot_off = -1;
-            b.free_bytes(b.tab1_lds, TAB1_RESERVE);
-            while (b.tabs1.size() % 8) b.tabs1.push_back(-1);
-            q.fprog[(size_t)loadtab_op].rows = (int)b.tabs1.size() * 2;      // bytes
-        };
-        auto enter_coop = [&]() {                     // h: this member's own sample -> the four samples of the group (rows of sample m come from member m)
-            b.flush_xchg();
-            b.cur_samp = -1;
-            enter_multi();
-            LT h4 = b.talloc(ch, H, W);
-            b.emit_xchg(h4, &h);
-            b.tfree(h);
-            h = h4; in_coop = true;
-        };
-        auto leave_coop = [&]() {                     // back to the member's own sample: its rows of the complete four-sample tensor
-            b.flush_xchg();
-            b.cur_samp = 0;
-            LT own = b.talloc(ch, H, W);
-            b.copy_t(own, h);
-            q.fprog.back().a_hw = own.hw(); q.fprog.back().a_mstride = own.hw() * h.rs * 4;
-            b.tfree(h);
-            h = own; in_coop = false;
-            leave_multi();
-        };
-        if (multi && !coop) {
-            enter_multi();
-            h = b.talloc(ch, H, W);
-            b.gather_g(h, hand_down);
-        }
-        int coop_level = -1;
-        for (int i = 1; i < nlev; ++i) {
-            if (coop && !in_coop && H * W == 4) { enter_coop(); coop_level = i; }       // 4 pixels per sample: 4 samples = one 16-row MFMA tile
-            for (int j = 0; j < nrb; ++j, ++d) {
-                const BlockSpec& bs = L.down[(size_t)d];
-                h = fused_resblock(b, bs.name, h, bs.cout, dense_off[bs.name]);
-                ch = bs.cout;
-                if (bs.attn) h = fused_attn(b, "down_attn." + std::to_string(d), h);
-                hs.push_back({b.spill_store(h), ch, H, W});
-            }
-            hs.push_back(hs.back());
-            if (i != nlev - 1) {
-                const int Ho = (H + 1 - 3) / 2 + 1, Wo = (W + 1 - 3) / 2 + 1;
-                LT o = b.talloc(ch, Ho, Wo);
-                const std::string nm = "downsample." + std::to_string(i) + ".Conv_0";
-                b.conv(h, H, W, Ho, Wo, 2, 0, 9, nm, 0, ch, nm + ".bias", 0, 0, &o, 1.f, -1, nullptr, nullptr, "", "");
-                b.tfree(h);
-                h = o; H = Ho; W = Wo;
-            }
-        }
-        if (coop && !in_coop) b.fail_("no level of exactly 4 pixels per sample: nothing to share");
-        h = fused_resblock(b, "mid_block1", h, ch, dense_off["mid_block1"]);
-        h = fused_resblock(b, "mid_block2", h, ch, dense_off["mid_block2"]);
-        for (int k = 0; k < nlev - 1; ++k) {          // up levels nlev-1 .. 1
-            for (int j = 0; j < nrb + 1; ++j, ++u) {
-                const BlockSpec& bs = L.up[(size_t)u];
-                HS sk = hs.back();
-                hs.pop_back();
-                LT cat = b.talloc(ch + sk.C, sk.H, sk.W);
-                b.gather_cat(cat, h, sk.spill, sk.C);
-                b.tfree(h);
-                H = sk.H; W = sk.W;
-                h = fused_resblock(b, bs.name, cat, bs.cout, dense_off[bs.name]);
-                ch = bs.cout;
-                if (bs.attn) h = fused_attn(b, "up_attn." + std::to_string(u), h);
-            }
-            if (in_coop && nlev - 1 - k == coop_level) leave_coop();      // the levels above run per sample again
-            if (k != nlev - 2) {                       // upsample between two low levels stays in this section
-                LT o = b.talloc(ch, 2 * H, 2 * W);
-                const std::string nm = "upsample." + std::to_string(k) + ".Conv_0";
-                b.conv(h, 2 * H, 2 * W, 2 * H, 2 * W, 1, 1, 9, nm, 0, ch, nm + ".bias", 0, 0, &o, 1.f, -1, nullptr, nullptr, "", "");
-                b.tfree(h);
-                h = o; H *= 2; W *= 2;
-            }
-        }
-        if (in_coop) leave_coop();
-        if (multi && !coop) {
-            hand_up = b.spill_store(h); b.tfree(h);
-            leave_multi();
-        }
-        loadtab_idx = loadtab_op;
-    }
-    // ---- level 0, up path: once per sample slot
-    const int u0 = u, ch_low = ch, H_low = H, W_low = W;
-    const std::vector<HS> hs0 = hs;
-    for (int sl = 0; sl < nslot0; ++sl) {
-        b.cur_samp = sl;
-        u = u0; ch = ch_low; H = H_low; W = W_low; hs = hs0;
-        if (multi && !coop) { h = b.talloc(ch, H, W); b.gather_g(h, hand_up); }
-        if (nlev > 1) {                                // the upsample conv onto level 0's (even) grid
-            LT o = b.talloc(ch, 2 * H, 2 * W);
-            const std::string nm = "upsample." + std::to_string(nlev - 2) + ".Conv_0";
-            if (b.up_fold_ok(h, 2 * H, 2 * W, ch)) b.conv_up4(h, nm, ch, nm + ".bias", &o);
-            else b.conv(h, 2 * H, 2 * W, 2 * H, 2 * W, 1, 1, 9, nm, 0, ch, nm + ".bias", 0, 0, &o, 1.f, -1, nullptr, nullptr, "", "");
-            b.tfree(h);
-            h = o; H *= 2; W *= 2;
-        }
-        for (int j = 0; j < nrb + 1; ++j, ++u) {
-            const BlockSpec& bs = L.up[(size_t)u];
-            HS sk = hs.back();
-            hs.pop_back();
-            LT cat = b.talloc(ch + sk.C, sk.H, sk.W);
-            b.gather_cat(cat, h, sk.spill, sk.C);
-            b.tfree(h);
-            H = sk.H; W = sk.W;
-            h = fused_resblock(b, bs.name, cat, bs.cout, dense_off[bs.name]);
-            ch = bs.cout;
-            if (bs.attn) h = fused_attn(b, "up_attn." + std::to_string(u), h);
-        }
-        b.gn(h, "out_norm", true);
-        b.conv(h, H, W, H, W, 1, 1, 9, "out_conv", 0, a.channels, "out_conv.bias", 0, 2, nullptr, 1.f, -1, nullptr, nullptr, "", "");
-        b.tfree(h);
-    }
-    if (H != c->H || W != c->W) b.fail_("network output grid differs from the input grid");
-
-    *tab_used = (int)q.ftabs.size() * 2 + 16;
-    *tab1_used = (int)b.tabs1.size() * 2 + 16;
-    if (*tab_used > TAB_RESERVE && TAB_RESERVE != 8 * 1024) b.fail_("row tables exceed the reserved LDS region");
-    if (*tab1_used > TAB1_RESERVE && multi) b.fail_("low-resolution row tables exceed their LDS block");
-    int cmax = 16;
-    for (auto& o : q.fprog) if (o.kind == FOP_CONV) { cmax = std::max(cmax, o.main_ph.nch * 16); for (int s2 = 0; s2 < o.nsc; ++s2) cmax = std::max(cmax, o.sc[s2].nch * 16); }
-    if (cmax * 4 + 64 > zero_bytes) b.fail_("zero row too small");
-    if (b.failed && TAB_RESERVE == 8 * 1024 && *tab_used <= 8 * 1024) return 0;      // pass 1 only sizes the tables
-    if (b.failed) { q.why = b.why; return 0; }
-
-    // table offsets (shorts, relative) -> LDS byte offsets
-    auto tab_lds = [&](int ref) { return (ref >> 24) ? b.tab1_lds + (ref & 0xffffff) * 2 : (ref & 0xffffff) * 2; };
-    for (auto& o : q.fprog) {
-        if (o.kind == FOP_CONV) {
-            for (int t = 0; t < o.ntap; ++t) o.tab_off[t] = tab_lds(o.tab_off[t]);
-            for (int s2 = 0; s2 < o.nsc; ++s2) o.sc[s2].tab_off = tab_lds(o.sc[s2].tab_off);
-        } else if (o.kind == FOP_GATHER && o.a_map_off >= 0) {
-            o.a_map_off = tab_lds(o.a_map_off);
-        }
-    }
-    while (q.ftabs.size() % 8) q.ftabs.push_back(-1);
-    const size_t tab0_shorts = q.ftabs.size();                  // region 0 is what the kernel copies at start; region 1 follows it in the buffer
-    q.ftabs.insert(q.ftabs.end(), b.tabs1.begin(), b.tabs1.end());
-    q.spill_per_sample = b.spill_floats;
-    // spill slots are [slot][n][rows][C].  Co-operative program: the low-resolution slots are indexed by (workgroup, sample of its group),
-    // n = 4 * workgroup id + slot, so the buffer holds 4 * (largest grid) "samples" per slot
-    int coop_max_nb = 0, spill_n = c->max_batch;
-    if (coop) {
-        const int st = c->coop_stride, res = resident_workgroups();
-        const int max_groups = (res / (4 * st)) * st;                      // whole blocks of 4 * stride workgroup ids that are resident together
-        coop_max_nb = std::min(c->max_batch, 4 * max_groups);
-        if (coop_max_nb < 1) b.fail_("no room for one co-operative group");
-        const int grid_max = ceil_div(ceil_div(std::max(coop_max_nb, 1), 4), st) * 4 * st;
-        spill_n = 4 * grid_max;
-    }
-    if (b.failed) { q.why = b.why; return 0; }
-    HIP_OK(hip_alloc(q.d_spill, std::max<size_t>(q.spill_per_sample, 1) * (size_t)spill_n));
-    HIP_OK(hip_alloc(q.d_fprog, q.fprog.size()));
-    HIP_OK(hip_alloc(q.d_ftabs, q.ftabs.size()));
-    HIP_OK(hipMemcpy(q.d_ftabs.get(), q.ftabs.data(), q.ftabs.size() * sizeof(short), hipMemcpyHostToDevice));
-    // spill slots: [slot][n][rows][C] so a workgroup only ever touches its own sample's rows
-    for (auto& f : b.spill_fix) {
-        FOp& o = q.fprog[(size_t)f.op];
-        float* p = q.d_spill.get() + f.off * (size_t)spill_n;
-        if (f.which == 1) o.b_g = p; else if (f.which == 2) o.a_g = p; else o.g_out = p;
-    }
-    UnetArgs& fa = q.fargs;
-    fa = UnetArgs{};
-    fa.prog = q.d_fprog.get(); fa.nops = (int)q.fprog.size();
-    fa.tabs = q.d_ftabs.get(); fa.tab_bytes = (int)(tab0_shorts * sizeof(short)); fa.tab_base = 0;
-    if (loadtab_idx >= 0) q.fprog[(size_t)loadtab_idx].a_g = reinterpret_cast<const float*>(q.d_ftabs.get() + tab0_shorts);
-    fa.zero_off = TAB_RESERVE; fa.zero_bytes = zero_bytes;
-    fa.dense = c->d_dense.get(); fa.dense_stride = c->dense_total; fa.S = S;
-    fa.out_elems = c->H * c->W * a.channels;
-    if (coop) {
-        const int groups_max = ceil_div(coop_max_nb, 4);
-        const size_t xb = (size_t)groups_max * 2 * 4 * (size_t)b.xslot_granules * sizeof(unsigned long long);
-        HIP_OK(hip_alloc(q.d_xbuf, std::max<size_t>(xb, 16) / sizeof(unsigned long long)));
-        HIP_OK(hipMemset(q.d_xbuf.get(), 0, std::max<size_t>(xb, 16)));          // tags start at 0; epochs never are
-        HIP_OK(hip_alloc(q.d_coop_err, 4));
-        HIP_OK(hipMemset(q.d_coop_err.get(), 0, 16));
-        fa.coop = 1; fa.coop_stride = c->coop_stride; fa.xbuf = q.d_xbuf.get(); fa.xslot = b.xslot_granules;
-        fa.coop_err = q.d_coop_err.get();
-        if (const char* e = std::getenv("RDMI_COOP_TEST_BREAK")) fa.coop_break = atoi(e);
-        q.coop = true; q.n_xchg = b.n_xchg; q.max_nb = coop_max_nb;
-    }
-    q.fused_lds = (size_t)b.high_water;
-    if (const char* e = std::getenv("RDMI_UDBG")) fa.dbg = atoi(e);
-    if (std::getenv("RDMI_STAMPS") && (S == 1 || coop)) {       // diagnostic builds exist for the single-sample and the co-operative program
-        if (!c->d_stamps) HIP_OK(hip_alloc(c->d_stamps, 1024 + 200 * 8 + 8));
-        if (q.fprog.size() > 200) return fail("RDMI_STAMPS: program of %zu ops", q.fprog.size());
-        fa.stamps = c->d_stamps.get();
-    }
-    q.fdesc.clear();
-    for (auto& o : q.fprog) {
-        char buf[160];
-        const char* kn[] = {"GATHER", "STORE", "GN", "CONV", "ATTN", "LOADTAB", "XCHG"};
-        if (o.kind == FOP_CONV) snprintf(buf, sizeof buf, "CONV rows=%d mtiles=%d K=%dx%d(+%d) Cout=%d dst=%d%s", o.rows, o.mtiles, o.ntap, o.main_ph.nch * 16, o.nsc ? o.sc[0].nch * 16 : 0, o.Cout, o.dst_kind, o.gn_off >= 0 ? (o.gn_raw ? (o.coop ? " +GN(copy) coop" : " +GN(copy)") : (o.coop ? " +GN coop" : " +GN")) : (o.coop ? " coop" : ""));
-        else snprintf(buf, sizeof buf, "%s rows=%d C=%d", kn[o.kind], o.rows, o.C);
-        q.fdesc.push_back(buf);
-    }
-    q.ok = true;
-    return 0;
+    return build_fused_program(c, dense_off);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1687,6 +858,32 @@ int launch_attn(const AttnArgs& a, hipStream_t s) {
 
 const float* P(rdmi_ctx* c, const std::string& name) { return c->params[(size_t)c->pindex.at(name)].ptr; }
 
+struct FwdIn {
+    const float* x; int x_mod;            // x holds x_mod samples; sample n reads x[n % x_mod] (0: n)
+    const float* sig; int sig_mod;        // sigma or t per sample (n % sig_mod); null: every sample uses t_scalar
+    float t_scalar;
+    int t_is_time; float smin, ratio;
+    const float* labels; int label_rows;
+    float* out; int NB;
+    const float* tt_row = nullptr;        // sampler: precomputed time_mlp.2 output row (+ both biases) of this evaluation's t
+    const float* dense_rows = nullptr;    // sampler: precomputed Dense_0 outputs [NB][dense_total] of this evaluation (skips the whole embedding)
+    float drop_p = 0.f; const unsigned long long* seed_dev = nullptr;   // tiled training forward: Dropout_0 probability and the step's seed word (null: no dropout)
+};
+
+}  // namespace
+#include "tiled_plan.h"
+#include "fused_plan.h"
+namespace {
+
+// parameter-dependent pointers of the layer plan (every repack, every training step whose parameter storage moved)
+void bind_layer_params(rdmi_ctx* c) {
+    auto at = [&](int i) -> const float* { return i >= 0 ? c->params[(size_t)i].ptr : nullptr; };
+    for (auto& op : c->ops) {
+        if (op.kind == OP_CONV) { ConvArgs& a = op.conv; a.bias = at(op.p_bias); a.bias_sc = at(op.p_bias_sc); a.gamma = at(op.p_gamma); a.beta = at(op.p_beta); }
+        else { op.attn.gamma = at(op.p_gamma); op.attn.beta = at(op.p_beta); op.attn.b3 = at(op.p_b3); }
+    }
+}
+
 int do_repack(rdmi_ctx* c, hipStream_t s) {
     for (size_t i = 0; i < c->jobs.size(); ++i) {
         const Param& p = c->params[(size_t)c->job_param[i]];
@@ -1704,56 +901,13 @@ int do_repack(rdmi_ctx* c, hipStream_t s) {
         hipLaunchKernelGGL(pack_kernel, dim3(32, (unsigned)c->jobs.size()), dim3(RDMI_THREADS), 0, s, (const PackJob*)c->d_jobs.get());
     }
     HIP_OK(hipGetLastError());
-    // parameter-dependent pointers
-    for (auto& op : c->ops) {
-        if (op.kind == OP_CONV) {
-            ConvArgs& a = op.conv;
-            a.bias = P(c, op.p_bias);
-            a.bias_sc = op.p_bias_sc.empty() ? nullptr : P(c, op.p_bias_sc);
-            a.gamma = op.p_gamma.empty() ? nullptr : P(c, op.p_gamma);
-            a.beta = op.p_beta.empty() ? nullptr : P(c, op.p_beta);
-        } else {
-            op.attn.gamma = P(c, op.p_gamma); op.attn.beta = P(c, op.p_beta); op.attn.b3 = P(c, op.p_b3);
-        }
-    }
+    bind_layer_params(c);
     if (c->tiled) tiled_bind_params(c);
-    for (auto& q : c->progs) {
-        if (!q.ok) continue;
-        for (auto& f : q.fpatch) {
-            FOp& o = q.fprog[(size_t)f.op];
-            const float* p = f.param.empty() ? c->d_w.get() + f.arena_off : P(c, f.param);
-            switch (f.field) {
-                case FusedBuilder::F_GAMMA: o.gamma = p; break;
-                case FusedBuilder::F_BETA: o.beta = p; break;
-                case FusedBuilder::F_BIAS: case FusedBuilder::F_BIAS_ARENA: o.bias = p; break;
-                case FusedBuilder::F_BIAS2: o.bias2 = p; break;
-                case FusedBuilder::F_W: o.main_ph.w = p; break;
-                case FusedBuilder::F_SC0W: o.sc[0].w = p; break;
-                case FusedBuilder::F_SC1W: o.sc[1].w = p; break;
-            }
-        }
-        HIP_OK(hipMemcpyAsync(q.d_fprog.get(), q.fprog.data(), q.fprog.size() * sizeof(FOp), hipMemcpyHostToDevice, s));
-    }
-    if (c->fused_ready()) HIP_OK(hipStreamSynchronize(s));
+    if (c->fused) for (auto& q : c->fused->progs) if (q.ok) if (int e = bind_fused_params(c, q, s)) return e;
+    if (fused_ready(c)) HIP_OK(hipStreamSynchronize(s));
     c->packed_valid = true;
     return 0;
 }
-
-struct FwdIn {
-    const float* x; int x_mod;            // x holds x_mod samples; sample n reads x[n % x_mod] (0: n)
-    const float* sig; int sig_mod;        // sigma or t per sample (n % sig_mod); null: every sample uses t_scalar
-    float t_scalar;
-    int t_is_time; float smin, ratio;
-    const float* labels; int label_rows;
-    float* out; int NB;
-    const float* tt_row = nullptr;        // sampler: precomputed time_mlp.2 output row (+ both biases) of this evaluation's t
-    const float* dense_rows = nullptr;    // sampler: precomputed Dense_0 outputs [NB][dense_total] of this evaluation (skips the whole embedding)
-    float drop_p = 0.f; const unsigned long long* seed_dev = nullptr;   // tiled training forward: Dropout_0 probability and the step's seed word (null: no dropout)
-};
-
-}  // namespace
-#include "tiled_plan.h"
-namespace {
 
 int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
     const rdmi_arch& a = c->arch;
@@ -1801,50 +955,12 @@ int run_forward(rdmi_ctx* c, const FwdIn& f, hipStream_t s) {
                     "GTO-Halo model run the exact-fp32 plans");
     if (c->tiled) return run_tiled(c, f, s);
     // ---- the U-Net: one workgroup-resident launch (csrc/unet_kernel.h) ...
-    const rdmi_ctx::FusedProg* fq = (c->use_fused && !c->debug_taps) ? c->pick(f.NB) : nullptr;
+    const FusedProg* fq = (c->use_fused && !c->debug_taps && c->fused) ? c->fused->pick(f.NB) : nullptr;
     if (c->in_train_forward) {      // one sample per workgroup pays while the batch fits the chip in about one wave of workgroups; beyond that the layer plan (bf16 MFMA) is faster
         static const int fused_upto = [] { const char* e = std::getenv("RDMI_TRAIN_FUSED_UPTO"); return e ? atoi(e) : 2 * std::max(resident_workgroups(), 1); }();
-        fq = (c->train_prog >= 0 && c->progs[(size_t)c->train_prog].ok && f.NB <= fused_upto) ? &c->progs[(size_t)c->train_prog] : nullptr;
+        fq = (c->fused && f.NB <= fused_upto) ? c->fused->training() : nullptr;
     }
-    if (fq) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(unet_wg_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(unet_wg_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>((unet_wg_kernel<false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>((unet_wg_kernel<false, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>((unet_wg_kernel<true, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>((unet_wg_kernel<false, false, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
-        UnetArgs ua = fq->fargs;
-        ua.x_in = f.x; ua.x_mod = f.x_mod; ua.out = f.out; ua.NB = f.NB;
-        unsigned nwg = (unsigned)ceil_div(f.NB, fq->S);
-        if (fq->coop) {          // groups of four workgroups, whole blocks of 4 * stride ids; every launch gets fresh exchange tags
-            nwg = (unsigned)(ceil_div(ceil_div(f.NB, 4), ua.coop_stride) * 4 * ua.coop_stride);
-            ua.epoch_base = c->coop_epoch;
-            c->coop_epoch += (unsigned)fq->n_xchg;
-            if (c->coop_epoch > 0xfff00000u) c->coop_epoch = 0;        // tags only have to differ from the two previous uses of a slot
-        }
-        if (f.dense_rows) ua.dense = f.dense_rows;
-        double fl = 0;
-        for (auto& op : c->ops) fl += op.flops_per_sample;
-        ProfScope ps(c, s, "unet_wg_kernel", fl * f.NB);
-        c->last_prog = (int)(fq - c->progs.data());
-        if (fq->train) {
-            ua.drop_p = c->train_drop_p; ua.seed_dev = c->train_seed_dev;
-            hipLaunchKernelGGL((unet_wg_kernel<false, false, false, true>), dim3(nwg), dim3(UW_THREADS), fq->fused_lds, s, ua);
-            HIP_OK(hipGetLastError());
-            return 0;
-        }
-        if ((ua.stamps || ua.dbg) && fq->S == 1) hipLaunchKernelGGL(unet_wg_kernel<true>, dim3(nwg), dim3(UW_THREADS), fq->fused_lds, s, ua);   // diagnostic build
-        else if ((ua.stamps || ua.dbg) && fq->coop) hipLaunchKernelGGL((unet_wg_kernel<true, true, true>), dim3(nwg), dim3(UW_THREADS), fq->fused_lds, s, ua);
-        else if (fq->coop) hipLaunchKernelGGL((unet_wg_kernel<false, true, true>), dim3(nwg), dim3(UW_THREADS), fq->fused_lds, s, ua);
-        else if (fq->S > 1) hipLaunchKernelGGL((unet_wg_kernel<false, true>), dim3(nwg), dim3(UW_THREADS), fq->fused_lds, s, ua);
-        else hipLaunchKernelGGL(unet_wg_kernel<false>, dim3(nwg), dim3(UW_THREADS), fq->fused_lds, s, ua);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
+    if (fq) return run_fused(c, *fq, f, s);
     // ---- ... or the layer-by-layer plan (debug taps, shapes the fused planner cannot fit in LDS)
     for (auto& op : c->ops) {
         if (op.kind == OP_CONV) {
@@ -1896,17 +1012,18 @@ extern "C" {
 
 const char* rdmi_last_error(void) { return g_err.c_str(); }
 int rdmi_debug_op_cycles(rdmi_ctx* c, long long* host, int cap, const char** desc, int desc_cap) {
-    if (!c || !c->d_stamps || !c->fused_ready()) return 0;
-    const rdmi_ctx::FusedProg& q0 = c->progs[(size_t)std::min<int>(std::max(c->last_prog, 0), (int)c->progs.size() - 1)];     // the program of the last launch
+    if (!c || !fused_ready(c) || !c->fused->d_stamps) return 0;
+    const long long* d_stamps = c->fused->d_stamps.get();
+    const FusedProg& q0 = c->fused->progs[(size_t)std::min<int>(std::max(c->fused->last_prog, 0), (int)c->fused->progs.size() - 1)];     // the program of the last launch
     const int n = (int)q0.fprog.size();
     std::vector<long long> st((size_t)n + 1);
     if (n > 1000) return 0;
-    if (hipMemcpy(st.data(), c->d_stamps.get(), st.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (hipMemcpy(st.data(), d_stamps, st.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     for (int i = 0; i < n && i < cap; ++i) host[i] = st[(size_t)i + 1] - st[(size_t)i];
     // fine stamps of CONV ops (entry, ring issued, first B landed, main done, shortcut done, epilogue done) follow at cap/2
     {
         std::vector<long long> fs((size_t)n * 8);
-        if (hipMemcpy(fs.data(), c->d_stamps.get() + 1024, fs.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipMemcpy(fs.data(), d_stamps + 1024, fs.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess)
             for (int i = 0; i < n && 256 + i * 8 + 7 < cap; ++i)
                 for (int k = 0; k < 8; ++k) host[256 + i * 8 + k] = fs[(size_t)i * 8 + k] - st[(size_t)i];
     }
@@ -1915,8 +1032,8 @@ int rdmi_debug_op_cycles(rdmi_ctx* c, long long* host, int cap, const char** des
 }
 
 int rdmi_debug_program(rdmi_ctx* c, int prog, int* S, int* coop, int* train, const char** desc, int desc_cap) {
-    if (!c || prog < 0 || prog >= (int)c->progs.size() || !c->progs[(size_t)prog].ok) return -1;
-    const rdmi_ctx::FusedProg& q = c->progs[(size_t)prog];
+    if (!c || !c->fused || prog < 0 || prog >= (int)c->fused->progs.size() || !c->fused->progs[(size_t)prog].ok) return -1;
+    const FusedProg& q = c->fused->progs[(size_t)prog];
     if (S) *S = q.S;
     if (coop) *coop = q.coop ? 1 : 0;
     if (train) *train = q.train ? 1 : 0;
@@ -1942,21 +1059,24 @@ const char* rdmi_path_info(rdmi_ctx* c) {
         long n_resize = 0;
         for (auto& l : c->tiled->launches) n_resize += std::holds_alternative<TResizeL>(l.op);
         s += "; resize launches (h onto an odd skip grid): " + std::to_string(n_resize);
-    } else if (c->fused_ready() && c->use_fused && !c->debug_taps) {
-        s = "fused: workgroup-resident U-Net, " + std::to_string(c->progs[0].fprog.size()) + " ops, " + std::to_string(c->progs[0].fused_lds) + " B LDS";
-        for (size_t i = 1; i < c->progs.size(); ++i)
-            if (c->progs[i].coop)
-                s += c->progs[i].ok ? "; co-operative groups of 4 workgroups up to batch " + std::to_string(c->progs[i].max_nb) + " (" + std::to_string(c->progs[i].fprog.size()) + " ops, " + std::to_string(c->progs[i].n_xchg) + " exchanges, id stride " + std::to_string(c->coop_stride) + (c->use_coop ? ")" : ", disabled)")
-                                    : "; co-operative program unavailable (" + c->progs[i].why + ")";
-            else
-            s += c->progs[i].ok ? "; S=" + std::to_string(c->progs[i].S) + " samples/workgroup from batch " + std::to_string(c->s_min_wg * c->progs[i].S) + " (" + std::to_string(c->progs[i].fprog.size()) + " ops)"
-                                : "; S=" + std::to_string(c->progs[i].S) + " unavailable (" + c->progs[i].why + ")";
     } else {
-        s = "layers: " + std::to_string(c->ops.size()) + " launches" + (c->fused_ready() ? "" : " (fused unavailable: " + (c->progs.empty() ? std::string("not built") : c->progs[0].why) + ")");
+        const std::vector<FusedProg>& progs = c->fused->progs;      // every context that does not run the tiled plan has a FusedPlan
+        if (fused_ready(c) && c->use_fused && !c->debug_taps) {
+            s = "fused: workgroup-resident U-Net, " + std::to_string(progs[0].fprog.size()) + " ops, " + std::to_string(progs[0].fused_lds) + " B LDS";
+            for (size_t i = 1; i < progs.size(); ++i)
+                if (progs[i].coop)
+                    s += progs[i].ok ? "; co-operative groups of 4 workgroups up to batch " + std::to_string(progs[i].max_nb) + " (" + std::to_string(progs[i].fprog.size()) + " ops, " + std::to_string(progs[i].n_xchg) + " exchanges, id stride " + std::to_string(c->fused->coop_stride) + (c->fused->use_coop ? ")" : ", disabled)")
+                                        : "; co-operative program unavailable (" + progs[i].why + ")";
+                else
+                s += progs[i].ok ? "; S=" + std::to_string(progs[i].S) + " samples/workgroup from batch " + std::to_string(c->fused->s_min_wg * progs[i].S) + " (" + std::to_string(progs[i].fprog.size()) + " ops)"
+                                    : "; S=" + std::to_string(progs[i].S) + " unavailable (" + progs[i].why + ")";
+        } else {
+            s = "layers: " + std::to_string(c->ops.size()) + " launches" + (fused_ready(c) ? "" : " (fused unavailable: " + (progs.empty() ? std::string("not built") : progs[0].why) + ")");
+        }
+        for (auto& q : progs) if (q.train && !q.ok) s += "; fused training forward unavailable (" + q.why + ")";
+        if (c->fused->training())
+            s += "; training forward: fused program (" + std::to_string(c->fused->training()->fprog.size()) + " ops, layer outputs stashed for the backward)";
     }
-    for (auto& q : c->progs) if (q.train && !q.ok) s += "; fused training forward unavailable (" + q.why + ")";
-    if (c->train_prog >= 0 && c->progs[(size_t)c->train_prog].ok)
-        s += "; training forward: fused program (" + std::to_string(c->progs[(size_t)c->train_prog].fprog.size()) + " ops, layer outputs stashed for the backward)";
     if (c->train) s += "; input-gradient backward calls: " + std::to_string(c->train->input_dgrad_calls);
     return s.c_str();
 }
@@ -1975,9 +1095,10 @@ int rdmi_philox_normal(float* z, size_t n, unsigned long long seed, unsigned lon
 int rdmi_coop_status(rdmi_ctx* c, int* gave_up) {
     if (!c || !gave_up) return fail("null argument");
     *gave_up = 0;
-    for (auto& q : c->progs)
+    if (!c->fused) return 0;
+    for (auto& q : c->fused->progs)
         if (q.coop && q.d_coop_err) { int v = 0; HIP_OK(hipMemcpy(&v, q.d_coop_err.get(), sizeof v, hipMemcpyDeviceToHost)); *gave_up |= v; }
-    if (*gave_up) c->use_coop = false;       // the groups of this device were not co-resident once: later calls take the single-sample programs
+    if (*gave_up) c->fused->use_coop = false;       // the groups of this device were not co-resident once: later calls take the single-sample programs
     return 0;
 }
 const char* rdmi_version(void) {

@@ -388,9 +388,10 @@ int rdmi_enable_training(rdmi_ctx* c) {
     // in the GroupNorm_1 epilogues) instead of ~100 layer-plan launches.  RDMI_TRAIN_FUSED=0, or a shape the planner cannot fit,
     // keeps the layer plan's forward.
     const char* tf = getenv("RDMI_TRAIN_FUSED");
-    if (!c->tiled && c->fused_ready() && (!tf || atoi(tf) != 0)) {
-        if (int e2 = build_one_program(c, 1, false, true)) return e2;
-        if (c->progs.back().ok && c->progs.back().train) c->train_prog = (int)c->progs.size() - 1;
+    if (!c->tiled && fused_ready(c) && (!tf || atoi(tf) != 0)) {
+        try { e = build_one_program(c, 1, false, true); } catch (const std::exception& ex) { e = fail("training program: %s", ex.what()); }
+        if (e) return e;
+        if (c->fused->progs.back().ok && c->fused->progs.back().train) c->fused->train_prog = (int)c->fused->progs.size() - 1;
     }
     c->train = std::move(T);
     return 0;
@@ -422,33 +423,12 @@ int train_refresh_params(rdmi_ctx* c, TrainPlan& T, hipStream_t s) {
         T.m_jobs_bwd = T.jobs;
         HIP_OK(hipMemcpyAsync(T.d_jobs.get(), T.m_jobs_bwd.data(), T.m_jobs_bwd.size() * sizeof(PackJob), hipMemcpyHostToDevice, s));
     }
-    for (auto& op : c->ops) {
-        if (op.kind == OP_CONV) {
-            ConvArgs& a = op.conv;
-            a.bias = P(c, op.p_bias);
-            a.bias_sc = op.p_bias_sc.empty() ? nullptr : P(c, op.p_bias_sc);
-            a.gamma = op.p_gamma.empty() ? nullptr : P(c, op.p_gamma);
-            a.beta = op.p_beta.empty() ? nullptr : P(c, op.p_beta);
-        } else { op.attn.gamma = P(c, op.p_gamma); op.attn.beta = P(c, op.p_beta); op.attn.b3 = P(c, op.p_b3); }
-    }
-    if (c->train_prog >= 0) {
-        rdmi_ctx::FusedProg& q = c->progs[(size_t)c->train_prog];
+    bind_layer_params(c);
+    if (c->fused && c->fused->train_prog >= 0) {
+        FusedProg& q = c->fused->progs[(size_t)c->fused->train_prog];
         const unsigned long long h = param_ptr_hash(c) | 1ull;
         if (q.ok && T.fprog_hash != h) {
-            for (auto& f : q.fpatch) {
-                FOp& o = q.fprog[(size_t)f.op];
-                const float* p = f.param.empty() ? c->d_w.get() + f.arena_off : P(c, f.param);
-                switch (f.field) {
-                    case FusedBuilder::F_GAMMA: o.gamma = p; break;
-                    case FusedBuilder::F_BETA: o.beta = p; break;
-                    case FusedBuilder::F_BIAS: case FusedBuilder::F_BIAS_ARENA: o.bias = p; break;
-                    case FusedBuilder::F_BIAS2: o.bias2 = p; break;
-                    case FusedBuilder::F_W: o.main_ph.w = p; break;
-                    case FusedBuilder::F_SC0W: o.sc[0].w = p; break;
-                    case FusedBuilder::F_SC1W: o.sc[1].w = p; break;
-                }
-            }
-            HIP_OK(hipMemcpyAsync(q.d_fprog.get(), q.fprog.data(), q.fprog.size() * sizeof(FOp), hipMemcpyHostToDevice, s));
+            if (int e = bind_fused_params(c, q, s)) return e;
             T.fprog_hash = h;
         }
     }
