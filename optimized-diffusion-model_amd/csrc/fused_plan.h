@@ -275,6 +275,20 @@ struct FusedBuilder {
     // normalised is the output of the CONV op emitted just before (only STOREs in between), has 4-channel groups and the conv's tiling
     // gives every wave a single pass, the GroupNorm is folded into that conv's epilogue (FOp::gn_*) and no op is emitted.
     // drop_block (training program): this activation is Conv_1's input in res block drop_block, the layer-plan op of that exact name, whose Dropout_0 acts on it.
+    static int conv_wave_rows(int ntiles) {          // WM of fop_conv: the 8 waves as WN along the column tiles x WM along the row tiles
+        const int lWN = (ntiles >= 8 && (ntiles & 7) == 0) ? 3 : (ntiles >= 4 ? 2 : (ntiles >= 2 ? 1 : 0));
+        return UW_WAVES >> lWN;
+    }
+    // Every single-sample fused GroupNorm of the finished program: the reader's slot count covers exactly the wave rows that park sums.
+    void check_gn_slots() {
+        for (size_t i = 0; i < prog.fprog.size(); ++i) {
+            const FOp& o = prog.fprog[i];
+            if (o.kind != FOP_CONV || o.gn_off < 0 || o.samp < 0) continue;
+            const int WM = conv_wave_rows(o.Cout_pad >> 4);
+            if (o.mtiles < 1 || o.mtiles > 4 * WM || o.gn_nslots != std::min(WM, o.mtiles) * 4 || (o.Cout / 4) * o.gn_nslots * 8 > 1024)
+                fail_("fused GroupNorm of op " + std::to_string(i) + ": " + std::to_string(o.gn_nslots) + " partial-sum slots for " + std::to_string(o.mtiles) + " row tiles over " + std::to_string(WM) + " wave rows");
+        }
+    }
     bool try_fuse_gn(const LT& t, const std::string& pre, bool act, const LT* src, const std::string& drop_block) {
         if (!gn_fuse) return false;
         const LT& in = src ? *src : t;
@@ -286,13 +300,15 @@ struct FusedBuilder {
         if (p.kind != FOP_CONV || p.dst_kind != 0 || p.gn_off >= 0 || p.dst_off != in.off || p.dst_rs != in.rs) return false;
         if (p.Cout != t.C || p.rows != t.rows() || t.C % 4 != 0 || std::min(t.C / 4, 32) * 4 != t.C) return false;      // Cg == 4 only
         const int ntiles = p.Cout_pad >> 4;
-        const int lWN = (ntiles >= 8 && (ntiles & 7) == 0) ? 3 : (ntiles >= 4 ? 2 : (ntiles >= 2 ? 1 : 0));      // as fop_conv
-        const int WN = 1 << lWN, WM = UW_WAVES >> lWN;
+        const int WM = conv_wave_rows(ntiles), WN = UW_WAVES / WM;
         if (ntiles > WN || p.mtiles > 4 * WM) return false;                    // a wave would make several passes
-        const int nslots = p.samp >= 0 ? WM * 4 : 4;
-        if (p.samp >= 0) { if ((t.C / 4) * nslots * 8 > 1024) return false; }
-        else if (multi_slot_off < 0 || t.ns * (t.C / 4) * 32 > 4096 || (t.hw() != 16 && t.hw() != 4)) return false;
-        p.gn_off = t.off; p.gn_rs = t.rs; p.gn_act = act ? 1 : 0; p.gn_raw = src ? 1 : 0;
+        // Single-sample form: wave row wm parks its partial sums in slots wm * 4 + kq (fconv_epi) and the reader adds slots 0 .. nslots - 1
+        // (fconv_gn_apply, two per float4).  Only wave rows that own a row tile enter fop_conv's tile loop, so the reader must stop at
+        // min(WM, mtiles) * 4: the slots of the other wave rows hold whatever the op before left in LDS.  (The room check keeps the full
+        // WM * 4, so which GroupNorms fold does not depend on the conv's height.)
+        const int nslots = p.samp >= 0 ? std::min(WM, p.mtiles) * 4 : 4;
+        if (p.samp >= 0) { if ((t.C / 4) * WM * 4 * 8 > 1024) return false; }
+        else if (multi_slot_off < 0 || t.ns * (t.C / 4) * 32 > 4096 || (t.hw() != 16 && t.hw() != 4)) return false;        p.gn_off = t.off; p.gn_rs = t.rs; p.gn_act = act ? 1 : 0; p.gn_raw = src ? 1 : 0;
         p.gn_slot_off = p.samp >= 0 ? gn_slot_off : multi_slot_off; p.gn_nslots = nslots;
         p.eps = 1e-6f; p.inv_cnt = 1.0f / (float)(4 * t.hw());
         patch(j, F_GAMMA, param(pre + ".weight")); patch(j, F_BETA, param(pre + ".bias"));
@@ -725,6 +741,7 @@ int build_fused_program_pass(rdmi_ctx* c, FusedProg& q, int S, int TAB_RESERVE, 
     int cmax = 16;
     for (auto& o : q.fprog) if (o.kind == FOP_CONV) cmax = std::max(cmax, o.main_ph.nch * 16);
     if (cmax * 4 + 64 > zero_bytes) b.fail_("zero row too small");
+    b.check_gn_slots();
     if (b.failed && TAB_RESERVE == 8 * 1024 && *tab_used <= 8 * 1024) return 0;      // pass 1 only sizes the tables
     if (b.failed) { q.why = b.why; return 0; }
 
