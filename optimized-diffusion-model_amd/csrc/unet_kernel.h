@@ -28,6 +28,13 @@
 #define UW_PF_KS1 4       // co-operative single-row-tile convs: a wave's K slice is 9-36 steps.  Measured: 4 and 9 equal (15.5 k cycles per 9x128 conv), 18 slower
                           // (18.2 k: the whole 147 KB slice of a CU is requested before the first MFMA and arrives at the L2->CU rate, nothing overlaps)
 #endif
+#ifndef UW_GB
+#define UW_GB 2           // GATHER: channel quads per work-item whose loads are in flight together.  Measured: 2 beats 3, 4
+                          // and 8 -- every quad of a batch is unrolled code, and the interpreter's code size costs more than the round trips save
+#endif
+#ifndef UW_GN_ROUND
+#define UW_GN_ROUND 1     // GN: rows per work-item normalised per round of the apply loop (divides 6).  Measured: 1 beats 2 and 3 (code size again)
+#endif
 #ifndef UW_PRIO
 #define UW_PRIO 0
 #endif
@@ -58,7 +65,7 @@ struct FPhase {            // one K-phase of a contraction: A rows come from an 
 
 struct FOp {
     int kind;
-    // ---- GATHER: dst[row][0:CA+CB] = concat(A[map(row)], B[row]); sources in LDS or global ([n][rows][C])
+    // ---- GATHER: dst[row][0:CA+CB] = concat(A[map(row)], B[row]); A in LDS or global ([n][rows][C]), B global and only beside an A in LDS
     // ---- STORE : global[n][rows][C] = LDS tensor
     // ---- GN    : in-place GroupNorm (+SiLU when act) of an LDS tensor
     // ---- CONV  : dst = scale * (sum_phases A_phase . W_phase + bias [+bias2] [+dense[n]] [+resid])
@@ -66,7 +73,7 @@ struct FOp {
     int dst_off, dst_rs, rows, C;                 // generic destination / tensor description
     int CA, CB;                                   // GATHER
     int a_off, a_rs, a_hw, a_mod, a_map_off;      // GATHER source A: a_off < 0 -> global a_g ([n % a_mod][a_hw][CA])
-    int b_off, b_rs;                              // GATHER source B: b_off < 0 -> global b_g ([n][rows][CB])
+    int b_off, b_rs;                              // GATHER source B: always global b_g ([n][rows][CB]); b_off / b_rs are not read
     const float* a_g; const float* b_g;
     float* g_out;                                 // STORE / CONV(dst_kind 2) global destination
     int G, act; float eps;                        // GN (src_off >= 0: read from that LDS tensor, write dst: fused copy)
@@ -130,8 +137,8 @@ struct UnetArgs {
     int NB;
     int S;                                        // samples per workgroup: workgroup b owns samples b*S .. b*S+S-1 (clamped to NB-1)
     int dbg;                                      // diagnostic ablations (0 in production; results are wrong when set): bit 2 skips GN
-                                                  // bodies, bit 3 CONV, bit 4 ATTN, bit 5 GATHER/STORE, bits 6/7 GN statistics / apply,
-                                                  // bit 8 conv epilogues, bit 9 conv main loops (scripts/gpu_ablate.py)
+                                                  // bodies, bit 3 CONV, bit 4 ATTN, bit 5 GATHER/STORE, bit 6 the GroupNorm op inside fop_gn
+                                                  // (statistics and apply are one pass; bit 7 is retired), bit 8 conv epilogues, bit 9 conv main loops (scripts/gpu_ablate.py)
     long long* stamps;                            // diagnostic: per-op shader-clock stamps of workgroup 0 (null in production)
     // co-operative program: groups of four workgroups (ids b, b + coop_stride, b + 2*coop_stride, b + 3*coop_stride inside each block of
     // 4*coop_stride ids: with stride 8 the four sit on one XCD under round-robin placement -- speed only, never correctness)
@@ -175,11 +182,11 @@ __device__ __forceinline__ int samp_of(int samp, int hw_shift, int row) { return
 
 template <bool MS>
 __device__ __forceinline__ void fop_gather(const OpW& w, const UnetArgs& u, int n0, int ncap, int member, int tid) {
-    struct { int C, rows, dst_off, dst_rs, CA, CB, a_off, a_rs, a_hw, a_mod, a_map_off, b_off, b_rs, samp, hw_shift; const float* a_g; const float* b_g; } o;
+    struct { int C, rows, dst_off, dst_rs, CA, CB, a_off, a_rs, a_hw, a_mod, a_map_off, samp, hw_shift; const float* a_g; const float* b_g; } o;
     o.C = OPI(w, C); o.rows = OPI(w, rows); o.dst_off = OPI(w, dst_off); o.dst_rs = OPI(w, dst_rs); o.CA = OPI(w, CA); o.CB = OPI(w, CB);
     o.a_off = OPI(w, a_off); o.a_rs = OPI(w, a_rs); o.a_hw = OPI(w, a_hw); o.a_mod = OPI(w, a_mod); o.a_map_off = OPI(w, a_map_off);
     if (MS && o.a_off >= 0) o.a_off += member * OPI(w, a_mstride);        // co-operative program: this member's rows of a multi-sample tensor
-    o.b_off = OPI(w, b_off); o.b_rs = OPI(w, b_rs); o.a_g = OPP(w, const float, a_g); o.b_g = OPP(w, const float, b_g);
+    o.a_g = OPP(w, const float, a_g); o.b_g = OPP(w, const float, b_g);
     o.samp = MS ? OPI(w, samp) : 0; o.hw_shift = MS ? OPI(w, hw_shift) : 0;
     const int Cd = o.C;                               // padded total channels (multiple of 4)
     const int c4n = Cd >> 2;
@@ -192,28 +199,70 @@ __device__ __forceinline__ void fop_gather(const OpW& w, const UnetArgs& u, int 
     const float* ag = from_x ? u.x_in : o.a_g;
     const int amod = from_x ? u.x_mod : o.a_mod;
     const int hw = o.samp >= 0 ? o.rows : (1 << o.hw_shift);          // destination rows per sample
+    // Beside the network input there are three forms -- a spilled tensor (A global), a concat of an LDS tensor with a spilled one
+    // (A in LDS through the row map, B global) and a plain LDS copy: at most ONE global source, and only A can be in LDS.  They
+    // run batched: a work-item's quads are taken GB at a time, and within a batch every load is issued before the first value is
+    // used -- row-map entries, then the global loads, then the LDS reads, then the LDS stores -- so a batch costs one global round
+    // trip instead of one per quad.  All decisions but "does this lane's quad come from that source" are wave-uniform and taken
+    // here, once; a lane whose quad does not come from a source reads the first quad of the source's row and the select drops it;
+    // quads beyond the tensor are read clamped to the last row and not stored.
+    const bool a_glob = o.a_off < 0;
+    if (!a_glob || ((o.CA & 3) == 0 && amod <= 0)) {
+        constexpr int GB = UW_GB;
+        const bool any_g = a_glob || o.CB > 0;
+        const float* gsrc = a_glob ? ag : o.b_g;                     // the global source: [n][g_hw][gC], destination channels gc0 .. gc0 + gC - 1
+        const int gC = a_glob ? o.CA : o.CB, g_hw = a_glob ? o.a_hw : hw, gc0 = a_glob ? 0 : o.CA;
+        const size_t g_ns = (size_t)g_hw * gC;
+        const float* lsrc = lds_f(a_glob ? 0 : o.a_off);
+        const int smul = o.samp >= 0 ? 0 : o.a_hw;                   // LDS source A: multi-sample tensors hold a_hw rows per sample
+        for (int i0 = tid; i0 < total; i0 += GB * UW_THREADS) {
+            int doff[GB], dc[GB], px[GB], nn[GB], sbase[GB], srow[GB];
+#pragma unroll
+            for (int b = 0; b < GB; ++b) {
+                const int r = min(row, o.rows - 1);
+                const int sl = samp_of(o.samp, o.hw_shift, r);
+                doff[b] = r * o.dst_rs + (c4 << 2); dc[b] = c4 << 2;
+                px[b] = o.samp >= 0 ? r : r - (sl << o.hw_shift);
+                nn[b] = min(n0 + sl, ncap - 1);
+                sbase[b] = sl * smul;
+                row += dpv; c4 += dc4;
+                if (c4 >= c4n) { c4 -= c4n; ++row; }
+            }
+#pragma unroll
+            for (int b = 0; b < GB; ++b) srow[b] = map ? (int)map[px[b]] : px[b];
+            f32x4 vg[GB], vl[GB];
+            if (any_g) {
+#pragma unroll
+                for (int b = 0; b < GB; ++b) {
+                    const int cg = dc[b] - gc0;
+                    vg[b] = ldg4(gsrc + nn[b] * g_ns + (unsigned)((a_glob ? srow[b] : px[b]) * gC + ((unsigned)cg < (unsigned)gC ? cg : 0)));
+                }
+            }
+            if (!a_glob) {
+#pragma unroll
+                for (int b = 0; b < GB; ++b)
+                    vl[b] = *reinterpret_cast<const f32x4*>(lsrc + (sbase[b] + srow[b]) * o.a_rs + (dc[b] < o.CA ? dc[b] : 0));
+            }
+#pragma unroll
+            for (int b = 0; b < GB; ++b) {
+                f32x4 val = {0.f, 0.f, 0.f, 0.f};
+                if (any_g && (unsigned)(dc[b] - gc0) < (unsigned)gC) val = vg[b];
+                if (!a_glob && dc[b] < o.CA) val = vl[b];
+                if (i0 + b * UW_THREADS < total) *reinterpret_cast<f32x4*>(dst + doff[b]) = val;
+            }
+        }
+        return;
+    }
+    // the network input (CA = 1 channel of x, one sample feeding several evaluations): a handful of scalar loads
     for (int i = tid; i < total; i += UW_THREADS) {
         const int c = c4 << 2;
         const int sl = samp_of(o.samp, o.hw_shift, row);             // sample slot and pixel of this destination row
         const int px = o.samp >= 0 ? row : row - (sl << o.hw_shift);
         const int n = min(n0 + sl, ncap - 1);
         f32x4 val = {0.f, 0.f, 0.f, 0.f};
-        if (c < o.CA) {
-            const int srow = map ? map[px] : px;
-            if (o.a_off >= 0) {                                      // LDS source: multi-sample tensors hold a_hw rows per sample
-                val = *reinterpret_cast<const f32x4*>(lds_f(o.a_off) + (size_t)((o.samp >= 0 ? 0 : sl * o.a_hw) + srow) * o.a_rs + c);
-            } else {
-                const int nA = amod > 0 ? n % amod : n;
-                const float* p = ag + ((size_t)nA * o.a_hw + srow) * o.CA + c;
-                if ((o.CA & 3) == 0) val = ldg4(p);
-                else
-                    for (int j = 0; j < 4; ++j)
-                        if (c + j < o.CA) val[j] = ldg1(p + j);
-            }
-        } else if (c < o.CA + o.CB) {
-            if (o.b_off >= 0) val = *reinterpret_cast<const f32x4*>(lds_f(o.b_off) + (size_t)row * o.b_rs + (c - o.CA));
-            else val = ldg4(o.b_g + ((size_t)n * hw + px) * o.CB + (c - o.CA));
-        }
+        const float* p = ag + ((size_t)(amod > 0 ? n % amod : n) * o.a_hw + (map ? map[px] : px)) * o.CA + c;
+        for (int j = 0; j < 4; ++j)
+            if (c + j < o.CA) val[j] = ldg1(p + j);
         *reinterpret_cast<f32x4*>(dst + (size_t)row * o.dst_rs + c) = val;
         row += dpv; c4 += dc4;
         if (c4 >= c4n) { c4 -= c4n; ++row; }
@@ -259,35 +308,57 @@ __device__ __forceinline__ float group_sum_rt(float v, int logT, int lane) {
     }
 }
 
-// GroupNorm (+SiLU) of an LDS tensor, in place or from a source tensor (fused copy).  Two-pass statistics with the
-// group's values held in REGISTERS between the passes (one LDS read per element), T lanes per group reduced by
-// xor-shuffles; the affine parameters of this work-item's fixed channel quad are prefetched by the caller one op
-// ahead (pgm/pbt) so their global latency never sits on the op-transition path.
+typedef float f32x2 __attribute__((vector_size(8)));
+__device__ __forceinline__ f32x2 ldg2(const float* p) {      // 8-byte load through the global address space (see ldg4)
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const f32x2 __attribute__((address_space(1))) * gptr_t;
+    return *(gptr_t)(p);
+#else
+    return *reinterpret_cast<const f32x2*>(p);
+#endif
+}
+
+// GroupNorm (+SiLU) of an LDS tensor, in place or from a source tensor (fused copy), in ONE pass over LDS.  T lanes share a
+// group: each reads its rows of the group's Cg channels once, the two-pass statistics form on those REGISTERS (T lanes reduced
+// by DPP row sums, which leave the full sum in every lane), and the lane that read a value normalises and writes it: no
+// statistics round trip through LDS, no barrier inside the op, no second read.  The group's gamma / beta are requested first
+// thing, so their global latency runs under the LDS reads and the two reductions.
 template <bool MS>
-__device__ __forceinline__ void fop_gn(const OpW& w, float* stat, int tid, f32x4 pgm, f32x4 pbt, int dbg = 0) {
+__device__ __forceinline__ void fop_gn(const OpW& w, int tid, int dbg = 0) {
     float* X0 = lds_f(OPI(w, dst_off));
     const int src_off = OPI(w, src_off);
     const float* S0 = src_off >= 0 ? lds_f(src_off) : X0;
     const int srs = src_off >= 0 ? OPI(w, src_rs) : OPI(w, dst_rs);
-    const int o_C = OPI(w, C), Cg = OPI(w, Cg), rs = OPI(w, dst_rs), o_act = OPI(w, act);
-    // multi-sample ops (samp < 0): the tensor is ns samples of hw rows; statistics are per sample ([ns][2 * G] in `stat`)
+    const int Cg = OPI(w, Cg), rs = OPI(w, dst_rs), o_act = OPI(w, act);
+    // multi-sample ops (samp < 0): the tensor is ns samples of hw rows; statistics are per sample
     const int o_samp = MS ? OPI(w, samp) : 0, hw_shift = MS ? OPI(w, hw_shift) : 0;
     const int o_rows = o_samp >= 0 ? OPI(w, rows) : (1 << hw_shift);
-    const int ns = o_samp >= 0 ? 1 : (OPI(w, rows) >> hw_shift);
     const int o_G = OPI(w, G);
     const float o_eps = OPF(w, eps);
     const int logT = OPI(w, logT), T = 1 << logT;     // 16 or 32 lanes per group
     const int g = tid >> logT, sub = tid & (T - 1);
     const float inv_cnt = OPF(w, inv_cnt);
-    const int mg_c4n = OPI(w, magic_c4n), mg_Cg = OPI(w, magic_Cg);
     // this lane's share of the group: rows sub, sub+T, ... (<= 6 rows for 96 pixels at T = 16), Cg <= 8 channels
     constexpr int MAXR = 6;
-    if (!(dbg & 64)) {
-    {
+    if (dbg & 64) return;
     // multi-sample ops: the ns * G (sample, group) pairs are spread over the workgroup (vg = sm * G + gq, T = 512 / (ns * G) lanes
-    // each): all samples' statistics form in ONE pass instead of one pass per sample
+    // each): all samples' statistics form in ONE pass instead of one pass per sample; a lane's rows belong to its sample
     const int sm = MS ? (g >> OPI(w, logG)) : 0, gq = MS ? (g & (o_G - 1)) : g;
     const float* base = S0 + (size_t)sm * o_rows * srs + gq * Cg;
+    float* obase = X0 + (size_t)sm * o_rows * rs + gq * Cg;
+    f32x4 gm0, gm1 = {0.f, 0.f, 0.f, 0.f}, bt0, bt1 = {0.f, 0.f, 0.f, 0.f};      // the group's affine parameters, channels 0-3 and 4-7
+    {
+        const float* gp = OPP(w, const float, gamma) + gq * Cg;
+        const float* bp = OPP(w, const float, beta) + gq * Cg;
+        if ((Cg & 3) == 0) {
+            gm0 = ldg4(gp); bt0 = ldg4(bp);
+            if (Cg > 4) { gm1 = ldg4(gp + 4); bt1 = ldg4(bp + 4); }
+        } else {
+            const f32x2 a0 = ldg2(gp), a1 = ldg2(gp + 2), a2 = ldg2(gp + 4), b0 = ldg2(bp), b1 = ldg2(bp + 2), b2 = ldg2(bp + 4);
+            gm0 = f32x4{a0[0], a0[1], a1[0], a1[1]}; gm1[0] = a2[0]; gm1[1] = a2[1];
+            bt0 = f32x4{b0[0], b0[1], b1[0], b1[1]}; bt1[0] = b2[0]; bt1[1] = b2[1];
+        }
+    }
     f32x4 v0[MAXR], v1[MAXR];
     float sum = 0.f;
     // Branch-free over rows: every lane loads its (clamped) rows back to back -- all reads in flight before the first
@@ -304,7 +375,6 @@ __device__ __forceinline__ void fop_gn(const OpW& w, float* stat, int tid, f32x4
             v0[k] = *reinterpret_cast<const f32x4*>(p);
             v1[k] = Cg > 4 ? *reinterpret_cast<const f32x4*>(p + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         } else {
-            typedef float f32x2 __attribute__((vector_size(8)));
             const f32x2 a0 = *reinterpret_cast<const f32x2*>(p), a1 = *reinterpret_cast<const f32x2*>(p + 2), a2 = *reinterpret_cast<const f32x2*>(p + 4);
             v0[k] = f32x4{a0[0], a0[1], a1[0], a1[1]};
             v1[k] = f32x4{a2[0], a2[1], 0.f, 0.f};
@@ -327,54 +397,45 @@ __device__ __forceinline__ void fop_gn(const OpW& w, float* stat, int tid, f32x4
         sq += rw[k] * q;
     }
     sq = group_sum_rt(sq, logT, tid & 63);
-    if (sub == 0) { stat[g * 2] = mean; stat[g * 2 + 1] = 1.0f / sqrtf(sq * inv_cnt + o_eps); }
-    }
-    }
-    // fixed channel quad per work-item: rows advance by rstep; work-items beyond rstep*c4n idle (C = 192)
-    const int c4n = o_C >> 2;
-    const int rstep = (UW_THREADS * mg_c4n) >> 16;      // floor(512 / c4n)
-    const int r0 = (tid * mg_c4n) >> 16, c = (tid - r0 * c4n) << 2;
-    const bool active = r0 < rstep;
-    lds_barrier();
-    if (active && !(dbg & 128)) {
-        if (!MS || ns == 1) {
-            f32x4 mu, rstd;
-            for (int j = 0; j < 4; ++j) { const int gg = ((c + j) * mg_Cg) >> 16; mu[j] = stat[2 * gg]; rstd[j] = stat[2 * gg + 1] * pgm[j]; }
-            for (int row = r0; row < o_rows; row += rstep) {
-                float* p = X0 + (size_t)row * rs + c;
-                f32x4 val = *reinterpret_cast<const f32x4*>(S0 + (size_t)row * srs + c);
+    // every lane of the group holds mean and sq: it normalises the values it read (real rows only) and writes them
+    const float rstd = 1.0f / sqrtf(sq * inv_cnt + o_eps);
+    f32x4 sc0, sc1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { sc0[j] = rstd * gm0[j]; sc1[j] = rstd * gm1[j]; }
+    // Code size (the interpreter has to stay near the instruction cache): the rows are taken in rounds of GNR with the register
+    // arrays shifted down between rounds, so the apply code exists GNR times, not MAXR times; a round no lane has a row in is
+    // not run (16-row tensors take one).
+    constexpr int GNR = UW_GN_ROUND;
+    static_assert(MAXR % GNR == 0, "apply rounds must tile the row share");
+#pragma unroll 1
+    for (int r0 = 0; r0 * T < o_rows; r0 += GNR) {
+#pragma unroll
+        for (int k = 0; k < GNR; ++k) {
+            const int v = sub + (r0 + k) * T;
+            if (v < o_rows) {
+                float* p = obase + (size_t)v * rs;
+                f32x4 y;
+#pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float y = (val[j] - mu[j]) * rstd[j] + pbt[j];
-                    val[j] = o_act ? silu_f(y) : y;
+                    const float a = (v0[k][j] - mean) * sc0[j] + bt0[j];
+                    y[j] = o_act ? silu_f(a) : a;
                 }
-                *reinterpret_cast<f32x4*>(p) = val;
-            }
-        } else {                       // all samples' rows in one sweep; a row's statistics are its sample's
-            const int total = ns * o_rows;
-            int gq[4];
-            for (int j = 0; j < 4; ++j) gq[j] = ((c + j) * mg_Cg) >> 16;
-            for (int row = r0; row < total; row += rstep) {
-                const int sb = (row >> hw_shift) * o_G;
-                float* p = X0 + (size_t)row * rs + c;
-                f32x4 val = *reinterpret_cast<const f32x4*>(S0 + (size_t)row * srs + c);
-                for (int j = 0; j < 4; ++j) {
-                    const float y = (val[j] - stat[2 * (sb + gq[j])]) * (stat[2 * (sb + gq[j]) + 1] * pgm[j]) + pbt[j];
-                    val[j] = o_act ? silu_f(y) : y;
+                if ((Cg & 3) == 0) *reinterpret_cast<f32x4*>(p) = y;
+                else { *reinterpret_cast<f32x2*>(p) = f32x2{y[0], y[1]}; *reinterpret_cast<f32x2*>(p + 2) = f32x2{y[2], y[3]}; }
+                if (Cg > 4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float a = (v1[k][j] - mean) * sc1[j] + bt1[j];
+                        y[j] = o_act ? silu_f(a) : a;
+                    }
+                    if ((Cg & 3) == 0) *reinterpret_cast<f32x4*>(p + 4) = y;
+                    else *reinterpret_cast<f32x2*>(p + 4) = f32x2{y[0], y[1]};
                 }
-                *reinterpret_cast<f32x4*>(p) = val;
             }
         }
+#pragma unroll
+        for (int k = 0; k + GNR < MAXR; ++k) { v0[k] = v0[k + GNR]; v1[k] = v1[k + GNR]; }
     }
-}
-
-// Affine parameters of the NEXT op when it is a GroupNorm: this work-item's fixed channel quad (see fop_gn).
-__device__ __forceinline__ void gn_prefetch(const OpW& nx, int tid, f32x4& pgm, f32x4& pbt) {
-    if (OPI(nx, kind) != FOP_GN) return;
-    const int c4n = OPI(nx, C) >> 2, mg = OPI(nx, magic_c4n);
-    const int r0 = (tid * mg) >> 16, c = (tid - r0 * c4n) << 2;
-    const float* gp = OPP(nx, const float, gamma);      // field reads are wave-uniform: keep them outside divergent code
-    const float* bp = OPP(nx, const float, beta);
-    if (r0 < ((UW_THREADS * mg) >> 16)) { pgm = ldg4(gp + c); pbt = ldg4(bp + c); }
 }
 
 // A-row byte offset for one table entry (-1 -> the shared zero row)
@@ -1409,30 +1470,23 @@ __global__ __launch_bounds__(UW_THREADS) void unet_wg_kernel(UnetArgs u) {
 #elif defined(__HIP_DEVICE_COMPILE__) && UW_PRIO == 2
     if (wave < 4) __builtin_amdgcn_s_setprio(1);
 #endif
-    float* stat = lds_f(u.zero_off + u.zero_bytes);      // [2 * 32] GroupNorm scratch right after the zero row
-    int* const failw = reinterpret_cast<int*>(stat) + 270;      // co-operative program: "an exchange gave up" (last word of the scratch block)
+    int* const failw = reinterpret_cast<int*>(lds_f(u.zero_off + u.zero_bytes)) + 270;      // co-operative program: "an exchange gave up" (last word of the scratch block)
     if (COOP && tid == 0) *failw = 0;
     if (DIAG && u.stamps && n == 0 && tid == 0) u.stamps[0] = clock64();
-    // descriptors are kept TWO ops ahead (cur, nxt resident; the load for pc+2 is in flight) so that small operands
-    // of the next op can be prefetched while the current one runs
+    // descriptors are kept TWO ops ahead (cur, nxt resident; the load for pc+2 is in flight): an op's fields are there when it starts
     OpW cur = opw_load(u.prog, lane);
     OpW nxt = opw_load(u.prog + (u.nops > 1 ? 1 : 0), lane);
-    f32x4 pgm = {1.f, 1.f, 1.f, 1.f}, pbt = {0.f, 0.f, 0.f, 0.f};
-    gn_prefetch(cur, tid, pgm, pbt);
     for (int pc = 0; pc < u.nops; ++pc) {
         const OpW nn = opw_load(u.prog + (pc + 2 < u.nops ? pc + 2 : u.nops - 1), lane);
         long long* fine = (DIAG && u.stamps && n == 0 && tid == ((u.dbg >> 16) & 7) * 64) ? u.stamps + 1024 + pc * 8 : nullptr;   // RDMI_UDBG bits 16-18: the wave whose fine stamps are kept
         const int kind = OPI(cur, kind);
-        if (DIAG && fine) fine[2] = clock64();
-        f32x4 ngm = pgm, nbt = pbt;
-        if (pc + 1 < u.nops) gn_prefetch(nxt, tid, ngm, nbt);
-        if (DIAG && fine) fine[3] = clock64();
+        if (DIAG && fine) fine[2] = fine[3] = clock64();
         const int skip = (DIAG && u.dbg) ? ((kind == FOP_GN ? 4 : kind == FOP_CONV ? 8 : kind == FOP_ATTN ? 16 : 32) & u.dbg) : 0;
         const bool multi = MS && OPI(cur, samp) < 0;
         switch (skip ? -1 : kind) {
             case FOP_GATHER: fop_gather<MS>(cur, u, multi ? n_spill : n, multi ? spill_cap : u.NB, COOP ? cm : 0, tid); break;
             case FOP_STORE: fop_store<MS>(cur, u, multi ? n_spill : n, multi ? spill_cap : u.NB, tid); break;
-            case FOP_GN: fop_gn<MS>(cur, stat, tid, pgm, pbt, DIAG ? u.dbg : 0); break;
+            case FOP_GN: fop_gn<MS>(cur, tid, DIAG ? u.dbg : 0); break;
             case FOP_CONV:
                 if (COOP && OPI(cur, coop)) fop_conv_coop<DIAG>(cur, u, n_multi, cm, wave, lane, fine);
                 else fop_conv<DIAG, MS && !COOP, TRAIN>(cur, u, multi ? n_multi : n, wave, lane, fine);      // co-operative: every multi-sample conv is a coop conv
@@ -1453,7 +1507,7 @@ __global__ __launch_bounds__(UW_THREADS) void unet_wg_kernel(UnetArgs u) {
         if (kind == FOP_STORE || (kind == FOP_CONV && OPI(cur, dst_kind) == 2)) __syncthreads();
         else lds_barrier();
         if (DIAG && u.stamps && n == 0 && tid == 0) u.stamps[pc + 1] = clock64();
-        cur = nxt; nxt = nn; pgm = ngm; pbt = nbt;
+        cur = nxt; nxt = nn;
     }
     if (COOP && *failw) {                                   // an exchange of this workgroup gave up: its result is not the network's -- make that loud
         const int E = (int)u.out_elems;

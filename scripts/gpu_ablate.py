@@ -1,4 +1,9 @@
-"""Kernel-time ablation (profiling aid): per-kernel mean times of 40 sampler updates under RDMI_DBG settings."""
+"""Kernel-time ablation (profiling aid): per-kernel mean times of 40 sampler updates under RDMI_UDBG settings.
+
+RDMI_UDBG is the bit mask of UnetArgs::dbg (csrc/unet_kernel.h): 4 skips the GN ops at the interpreter, 8 CONV, 16 ATTN,
+32 GATHER / STORE; 64 skips the GroupNorm inside fop_gn (the op is entered, its descriptor fields are read, nothing else);
+128 is retired (it was the apply half of the two-sweep GroupNorm: statistics and apply are one pass now); 256 conv epilogues,
+512 conv main loops.  Results are wrong when any bit is set; only the time is meaningful."""
 import os, sys, json, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r'''
